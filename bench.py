@@ -12,7 +12,14 @@ launched by the driver as one rank per GPU via torch.distributed.run; ranks
 sync with RCCL barriers around the timed region and the slowest rank's time
 is used (MAX all-reduce).
 
+A plain run does only what the headline figure needs: setup, warmup, the
+timed steps, the optional --dump-outputs files and the result line.
+Anything measured beyond that belongs behind --full (off by default; at
+present every figure in the result line comes out of the timed steps
+themselves, so --full adds nothing yet).
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
 """
 
 from __future__ import annotations
@@ -69,7 +76,66 @@ def parse_args():
     # staging rates (verify kernel runs at multi-TB/s; see profiles/).
     p.add_argument("--verify", type=int,
                    default=int(os.environ.get("EB_BENCH_VERIFY", "1")))
-    return p.parse_args()
+    # what the last timed step delivered, as DIR/<name>.npy (see dump_outputs)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None)
+    # measurements beyond the headline figure (none yet: latency percentiles
+    # and on-GPU verify are taken inside the timed steps, not in extra runs)
+    p.add_argument("--full", action="store_true")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.warmup < 0:
+        p.error("--warmup must be >= 0")
+    return args
+
+
+DUMP_SAMPLE_CHUNKS = 256     # x DUMP_SAMPLE_CHUNK bytes = 1 MiB of data,
+DUMP_SAMPLE_CHUNK = 4096     # 4 MiB as float32 (well under the 64 MB cap)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, path: str, file_size: int, last_res) -> None:
+    """Write what the last timed step delivered, one float .npy per array.
+
+    pass_totals.npy  float64 [entries, bytes, iops, workers_with_error]:
+                     the per-worker results finish_phase() returned for the
+                     last timed pass, summed over this rank's workers (the
+                     split between workers varies with dynamic slicing, the
+                     sums do not; latencies are timing, so they stay out).
+    data_sample.npy  float32 [chunks, chunk_bytes]: the dataset bytes the
+                     pass moved (for reads: what it read and verified in
+                     HBM; for seqwrite: what it wrote), taken at fixed,
+                     seeded 4 KiB-aligned offsets. The first and the last
+                     chunk of the file are always included.
+    sample_offsets.npy float64 [chunks]: file offset of each sampled chunk.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    totals = np.array([
+        sum(r["entries"] for r in last_res),
+        sum(r["bytes"] for r in last_res),
+        sum(r["iops"] for r in last_res),
+        sum(1 for r in last_res if r["error"]),
+    ], dtype=np.float64)
+    np.save(os.path.join(out_dir, "pass_totals.npy"), totals)
+
+    n_chunks = max(file_size // DUMP_SAMPLE_CHUNK, 1)
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    picks = rng.integers(0, n_chunks, size=DUMP_SAMPLE_CHUNKS, dtype=np.int64)
+    picks[0], picks[-1] = 0, n_chunks - 1
+    offsets = np.sort(picks) * DUMP_SAMPLE_CHUNK
+    sample = np.zeros((len(offsets), DUMP_SAMPLE_CHUNK), dtype=np.float32)
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        for i, off in enumerate(offsets):
+            buf = os.pread(fd, DUMP_SAMPLE_CHUNK, int(off))
+            sample[i, :len(buf)] = np.frombuffer(buf, dtype=np.uint8)
+    finally:
+        os.close(fd)
+    np.save(os.path.join(out_dir, "data_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "sample_offsets.npy"),
+            offsets.astype(np.float64))
 
 
 def main() -> int:
@@ -220,10 +286,13 @@ def main() -> int:
     weng = core.Engine(wcfg)
     weng.prepare()
 
+    last_res = []  # per-worker results of the most recent pass
+
     def run_pass(eng, phase, lat_hist=None):
         eng.start_phase(core.PHASES[phase])
         eng.wait_phase_done(-1)
         res = eng.finish_phase()
+        last_res[:] = res
         errs = [r["error"] for r in res if r["error"]]
         if errs:
             raise RuntimeError(f"bench phase failed: {errs}")
@@ -356,6 +425,8 @@ def main() -> int:
             }
         if args.workload == "randread":
             doc["config"]["iops_4k"] = int(total_bytes / 4096 / elapsed)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, path, args.filesize, last_res)
         print(json.dumps(doc), flush=True)
 
     # cleanup (tmpfs is shared RAM — do not leak multi-GiB files)

@@ -65,6 +65,15 @@ public:
         if (wantIoPoll) p.flags |= IORING_SETUP_IOPOLL;
 
         ringFd = (int)syscall(__NR_io_uring_setup, entries, &p);
+        // Unprivileged users: ring memory and registered buffers count
+        // against RLIMIT_MEMLOCK per user, and the kernel gives back what a
+        // closed ring held from a work queue, some time after close(). Rings
+        // of the phase or engine just torn down can so make this setup fail
+        // with ENOMEM for a moment: wait for the release (1 s at the most).
+        for (int tries = 0; ringFd < 0 && errno == ENOMEM && tries < 50; tries++) {
+            usleep(20 * 1000);
+            ringFd = (int)syscall(__NR_io_uring_setup, entries, &p);
+        }
         if (ringFd < 0 && wantSqPoll && (errno == EPERM || errno == EINVAL)) {
             // unprivileged: fall back to plain submission
             p.flags &= ~(unsigned)IORING_SETUP_SQPOLL;

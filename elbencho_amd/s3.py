@@ -767,7 +767,11 @@ class S3Worker(threading.Thread):
                 ex, clients, _ = self._pool
                 ex.shutdown(wait=True)
                 while not clients.empty():
-                    clients.get_nowait().close()
+                    c = clients.get_nowait()
+                    c.close()
+                    # drop the plane now: a failed task's traceback keeps
+                    # its client (a reference cycle) until the cyclic GC runs
+                    c.native = None
                 self._pool = None
             self.elapsed_us = self.elapsed_us or int(
                 (time.monotonic() - self.r.phase_start) * 1e6)

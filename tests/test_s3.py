@@ -523,6 +523,30 @@ def test_native_dataplane_released_after_run(mock_s3):
         assert core.http_dataplane_live() == 0
 
 
+def test_native_dataplane_released_after_failed_pipeline(mock_s3):
+    """A failed --iodepth run releases its native planes without the cyclic
+    GC: the failed task's traceback keeps its client alive in a reference
+    cycle, which must not keep the plane with it."""
+    import gc
+
+    from elbencho_amd import load_core
+
+    core = load_core()
+    c = S3Client(mock_s3, ACCESS_KEY, SECRET_KEY)
+    c.create_bucket("errrel")
+    c.put_object("errrel", "r0-f0", b"x" * (64 * 1024))  # only one of two
+    gc.collect()
+    before = core.http_dataplane_live()
+    gc.disable()
+    try:
+        rc = _cli(mock_s3, ["-r", "-t", "1", "-N", "2", "-s", "64k", "-b",
+                            "16k", "--iodepth", "4", "s3://errrel"])
+        assert rc != 0
+        assert core.http_dataplane_live() == before
+    finally:
+        gc.enable()
+
+
 @pytest.mark.parametrize("seed", range(10))
 def test_fuzz_native_endpoint_flags(seed, tmp_path):
     """Flag-combination fuzz against the native C++ endpoint with the

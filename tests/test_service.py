@@ -333,10 +333,12 @@ def test_service_reuse_after_interrupt(services, tmp_path):
     (reference /interruptphase semantics: reset, no quit)."""
     hosts = ",".join(f"127.0.0.1:{p}" for p in services)
     env = dict(os.environ, PYTHONPATH=REPO)
-    # long-running write (64 GiB would take minutes) with a 1s timelimit ->
-    # master interrupts the phase and reports failure
+    # long-running write (rate-limited to 64 MiB/s per thread, so 8 GiB
+    # takes a minute on any machine, however fast its tmpfs) with a 1s
+    # timelimit -> master interrupts the phase and reports failure
     res = run_master(["--hosts", hosts, "-w", "-t", "1", "-s", "8g", "-b", "1m",
-                      "--timelimit", "1", str(tmp_path / "big")])
+                      "--limitwrite", "64m", "--timelimit", "1",
+                      str(tmp_path / "big")])
     assert res.returncode != 0
     # the same services then run a normal benchmark cleanly
     res = run_master(["--hosts", hosts, "-w", "-r", "-t", "1", "-s", "1m",
