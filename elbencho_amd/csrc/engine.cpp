@@ -44,23 +44,25 @@ static inline uint64_t checksumValueAt(uint64_t alignedOff, uint64_t salt)
 
 void fillChecksumCPU(char* buf, uint64_t len, uint64_t fileOff, uint64_t salt)
 {
+    // pos/end are compared by difference only, so a range that ends at (or
+    // wraps past) 2^64 is handled like any other
     uint64_t pos = fileOff;
     uint64_t end = fileOff + len;
 
     // unaligned head: bytes of the u64 containing fileOff
-    while (pos < end && (pos & 7)) {
+    while (pos != end && (pos & 7)) {
         uint64_t v = checksumValueAt(pos & ~7ULL, salt);
         buf[pos - fileOff] = (char)((v >> (8 * (pos & 7))) & 0xff);
         pos++;
     }
     // aligned middle
-    while (pos + 8 <= end) {
+    while (end - pos >= 8) {
         uint64_t v = checksumValueAt(pos, salt);
         std::memcpy(buf + (pos - fileOff), &v, 8);
         pos += 8;
     }
     // tail
-    while (pos < end) {
+    while (pos != end) {
         uint64_t v = checksumValueAt(pos & ~7ULL, salt);
         buf[pos - fileOff] = (char)((v >> (8 * (pos & 7))) & 0xff);
         pos++;
@@ -72,12 +74,12 @@ uint64_t verifyChecksumCPU(const char* buf, uint64_t len, uint64_t fileOff, uint
     uint64_t pos = fileOff;
     uint64_t end = fileOff + len;
 
-    while (pos < end && (pos & 7)) {
+    while (pos != end && (pos & 7)) {
         uint64_t v = checksumValueAt(pos & ~7ULL, salt);
         if (buf[pos - fileOff] != (char)((v >> (8 * (pos & 7))) & 0xff)) return pos;
         pos++;
     }
-    while (pos + 8 <= end) {
+    while (end - pos >= 8) {
         uint64_t v = checksumValueAt(pos, salt);
         uint64_t got;
         std::memcpy(&got, buf + (pos - fileOff), 8);
@@ -87,7 +89,7 @@ uint64_t verifyChecksumCPU(const char* buf, uint64_t len, uint64_t fileOff, uint
         }
         pos += 8;
     }
-    while (pos < end) {
+    while (pos != end) {
         uint64_t v = checksumValueAt(pos & ~7ULL, salt);
         if (buf[pos - fileOff] != (char)((v >> (8 * (pos & 7))) & 0xff)) return pos;
         pos++;

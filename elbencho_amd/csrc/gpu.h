@@ -107,24 +107,35 @@ public:
     // async verify accumulating into persistent device counters; results
     // fetched (and reset) by fetchVerifyResult() — lets the caller batch
     // many blocks per stream synchronization
-    void verifyChecksumDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt);
+    // Same alignment contract as verifyChecksumDev. ldsVariant selects the
+    // LDS-tiled A/B kernel (tests and gpu_verify_bench only).
+    void verifyChecksumDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                bool ldsVariant = false);
     GpuVerifyResult fetchVerifyResult();
 
     // --- device-side buffer ops (hand-written gfx950 kernels) ---
 
     // Fill device buffer with xoshiro256++ random data (replaces curand).
+    // Requires len % 16 == 0 (one 16 B store per element); throws
+    // std::invalid_argument otherwise.
     void fillRandDev(int slot, uint64_t len, uint64_t seed, bool fastAlgo = false);
 
     // Integrity-checksum fill: u64 at 8-aligned file offset o gets value
-    // o + salt. Requires fileOff % 8 == 0 and len % 8 == 0.
+    // o + salt. Requires fileOff % 8 == 0 and len % 8 == 0; throws
+    // std::invalid_argument otherwise.
     void fillChecksumDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt);
 
     // Verify the checksum pattern on-device (LDS/wave-reduced mismatch count
-    // + first bad offset). Requires 8-aligned fileOff/len. Synchronizes.
-    GpuVerifyResult verifyChecksumDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt);
+    // + first bad offset). Requires fileOff % 8 == 0 and len % 8 == 0 (an odd
+    // final u64 is checked too); throws std::invalid_argument otherwise.
+    // Synchronizes.
+    GpuVerifyResult verifyChecksumDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                      bool ldsVariant = false);
 
     // Block-variance refill: first refillLen bytes random, remainder filled
-    // with one random u64 constant (defeats dedup). 8-aligned lengths.
+    // with one random u64 constant (defeats dedup). Requires len % 16 == 0
+    // (throws std::invalid_argument otherwise); refillLen is floored to a
+    // multiple of 16 and capped at len.
     void blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint64_t seed,
                            bool fastAlgo = false);
 

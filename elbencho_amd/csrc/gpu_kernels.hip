@@ -191,14 +191,17 @@ __global__ __launch_bounds__(256) void ebFillChecksumKernel(uint64_t* __restrict
 // Integrity verify: compare against the checksum pattern; one atomicAdd of
 // the wave-reduced mismatch count per wave, atomicMin for first bad offset.
 // out[0] = mismatch count, out[1] = first bad file offset (init UINT64_MAX).
+// n64 counts u64 words; an odd final word is compared by the first thread,
+// mirroring ebFillChecksumKernel, and feeds the same reduction.
 __global__ __launch_bounds__(256) void ebVerifyChecksumKernel(const ulonglong2* __restrict__ buf,
-                                                              uint64_t nVec2,
+                                                              uint64_t n64,
                                                               uint64_t fileOff,
                                                               uint64_t salt,
                                                               unsigned long long* __restrict__ out)
 {
     uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t nVec2 = n64 / 2;
 
     unsigned long long localBad = 0;
     unsigned long long localFirst = ~0ULL;
@@ -215,6 +218,14 @@ __global__ __launch_bounds__(256) void ebVerifyChecksumKernel(const ulonglong2* 
         if (v.y != exp1) {
             localBad++;
             if (off0 + 8 < localFirst) localFirst = off0 + 8;
+        }
+    }
+
+    if (tid == 0 && (n64 & 1)) { // odd final u64
+        uint64_t offT = fileOff + (n64 - 1) * 8;
+        if (((const uint64_t*)buf)[n64 - 1] != offT + salt) {
+            localBad++;
+            if (offT < localFirst) localFirst = offT;
         }
     }
 
@@ -238,9 +249,10 @@ __global__ __launch_bounds__(256) void ebVerifyChecksumKernel(const ulonglong2* 
 // LDS round-trip is pure overhead (no reuse), so this is expected to lose;
 // ebVerifyChecksumKernel is what the engine runs.
 __global__ __launch_bounds__(256) void ebVerifyChecksumLdsKernel(
-    const ulonglong2* __restrict__ buf, uint64_t nVec2, uint64_t fileOff,
+    const ulonglong2* __restrict__ buf, uint64_t n64, uint64_t fileOff,
     uint64_t salt, unsigned long long* __restrict__ out)
 {
+    const uint64_t nVec2 = n64 / 2;
     constexpr int VPT = 4; // vec2 per thread per tile: 256*4*16 B = 16 KiB LDS
     __shared__ ulonglong2 lds[256 * VPT];
     __shared__ unsigned long long blkBad, blkFirst;
@@ -277,6 +289,14 @@ __global__ __launch_bounds__(256) void ebVerifyChecksumLdsKernel(
             }
         }
         __syncthreads();
+    }
+
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n64 & 1)) { // odd final u64
+        uint64_t offT = fileOff + (n64 - 1) * 8;
+        if (((const uint64_t*)buf)[n64 - 1] != offT + salt) {
+            localBad++;
+            if (offT < localFirst) localFirst = offT;
+        }
     }
 
 #pragma unroll
@@ -617,14 +637,32 @@ uint64_t GpuCtx::timedElapsedUSec(int slot)
     return (uint64_t)(ms * 1000.0f);
 }
 
-void GpuCtx::verifyChecksumDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt)
+static void requireAligned(const char* what, uint64_t len, uint64_t lenAlign,
+                           uint64_t fileOff = 0)
 {
-    uint64_t nVec2 = len / 16;
-    if (!nVec2) return;
-    dim3 grid = gridForBytes(nVec2);
-    hipLaunchKernelGGL(ebVerifyChecksumKernel, grid, dim3(256), 0, impl->stream,
-                       (const ulonglong2*)impl->devBufs[slot], nVec2, fileOff, salt,
-                       impl->verifyOutDev);
+    if (len % lenAlign)
+        throw std::invalid_argument(std::string(what) + ": len " + std::to_string(len) +
+                                    " is not a multiple of " + std::to_string(lenAlign));
+    if (fileOff % 8)
+        throw std::invalid_argument(std::string(what) + ": fileOff " +
+                                    std::to_string(fileOff) + " is not a multiple of 8");
+}
+
+void GpuCtx::verifyChecksumDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                    bool ldsVariant)
+{
+    requireAligned("verifyChecksumDev", len, 8, fileOff);
+    uint64_t n64 = len / 8;
+    if (!n64) return;
+    dim3 grid = gridForBytes(n64 / 2);
+    if (ldsVariant)
+        hipLaunchKernelGGL(ebVerifyChecksumLdsKernel, grid, dim3(256), 0, impl->stream,
+                           (const ulonglong2*)impl->devBufs[slot], n64, fileOff, salt,
+                           impl->verifyOutDev);
+    else
+        hipLaunchKernelGGL(ebVerifyChecksumKernel, grid, dim3(256), 0, impl->stream,
+                           (const ulonglong2*)impl->devBufs[slot], n64, fileOff, salt,
+                           impl->verifyOutDev);
     HIP_CHECK(hipGetLastError());
     impl->verifyDirty = true;
 }
@@ -649,6 +687,7 @@ GpuVerifyResult GpuCtx::fetchVerifyResult()
 
 void GpuCtx::fillRandDev(int slot, uint64_t len, uint64_t seed, bool fastAlgo)
 {
+    requireAligned("fillRandDev", len, 16);
     uint64_t nVec2 = len / 16;
     uint64_t seq = ++impl->fillCallCounter;
     if (nVec2) {
@@ -669,6 +708,7 @@ void GpuCtx::fillRandDev(int slot, uint64_t len, uint64_t seed, bool fastAlgo)
 
 void GpuCtx::fillChecksumDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt)
 {
+    requireAligned("fillChecksumDev", len, 8, fileOff);
     uint64_t n64 = len / 8;
     if (!n64) return;
     dim3 grid = gridForBytes(n64);
@@ -677,15 +717,17 @@ void GpuCtx::fillChecksumDev(int slot, uint64_t len, uint64_t fileOff, uint64_t 
     HIP_CHECK(hipGetLastError());
 }
 
-GpuVerifyResult GpuCtx::verifyChecksumDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt)
+GpuVerifyResult GpuCtx::verifyChecksumDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                          bool ldsVariant)
 {
-    verifyChecksumDevAsync(slot, len, fileOff, salt);
+    verifyChecksumDevAsync(slot, len, fileOff, salt, ldsVariant);
     return fetchVerifyResult();
 }
 
 void GpuCtx::blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint64_t seed,
                                bool fastAlgo)
 {
+    requireAligned("blockVarRefillDev", len, 16);
     uint64_t nVec2 = len / 16;
     if (!nVec2) return;
     uint64_t refillVec2 = refillLen / 16;
@@ -714,7 +756,7 @@ void GpuCtx::blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint6
 double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev)
 {
     HIP_CHECK(hipSetDevice(dev));
-    const uint64_t nVec2 = len / 16;
+    const uint64_t n64 = len / 8;
     ulonglong2* buf = nullptr;
     unsigned long long* out = nullptr;
     HIP_CHECK(hipMalloc(&buf, len));
@@ -723,7 +765,7 @@ double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev)
 
     hipStream_t s;
     HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    dim3 grid = gridForBytes(nVec2);
+    dim3 grid = gridForBytes(n64 / 2);
 
     hipLaunchKernelGGL(ebFillChecksumKernel, gridForBytes(len / 8), dim3(256), 0, s,
                        (uint64_t*)buf, len / 8, 0, 7);
@@ -731,10 +773,10 @@ double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev)
     auto launch = [&] {
         if (lds)
             hipLaunchKernelGGL(ebVerifyChecksumLdsKernel, grid, dim3(256), 0, s,
-                               buf, nVec2, 0, 7, out);
+                               buf, n64, 0, 7, out);
         else
             hipLaunchKernelGGL(ebVerifyChecksumKernel, grid, dim3(256), 0, s,
-                               buf, nVec2, 0, 7, out);
+                               buf, n64, 0, 7, out);
     };
 
     launch(); // warmup

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <unistd.h>
 
 #include <fcntl.h>
@@ -322,15 +323,105 @@ PYBIND11_MODULE(_core, m)
         return py::bytes(ctx.hostBuf(0), len);
     }, py::arg("len"), py::arg("file_off"), py::arg("salt"), py::arg("dev") = 0);
 
-    m.def("gpu_verify_checksum", [](py::bytes data, uint64_t fileOff, uint64_t salt, int dev) {
+    // lds=true runs the LDS-tiled A/B kernel instead of the production one
+    m.def("gpu_verify_checksum", [](py::bytes data, uint64_t fileOff, uint64_t salt, int dev,
+                                    bool lds) {
         std::string buf = data;
         GpuCtx ctx(dev, 1, buf.size(), true);
         std::memcpy(ctx.hostBuf(0), buf.data(), buf.size());
         ctx.copyH2DAsync(0, buf.size());
         ctx.syncStream();
-        GpuVerifyResult r = ctx.verifyChecksumDev(0, buf.size(), fileOff, salt);
+        GpuVerifyResult r = ctx.verifyChecksumDev(0, buf.size(), fileOff, salt, lds);
         return py::make_tuple(r.numMismatches, r.firstBadFileOffset);
-    }, py::arg("data"), py::arg("file_off"), py::arg("salt"), py::arg("dev") = 0);
+    }, py::arg("data"), py::arg("file_off"), py::arg("salt"), py::arg("dev") = 0,
+       py::arg("lds") = false);
+
+    // --- test-only helpers for the bit-exact kernel tests (not for the engine) ---
+
+    // One xoshiro256++ stream of the CPU "balanced" fill (seeded with the
+    // same four splitmix64 outputs as the device Xoshiro256pp::seed), as n
+    // little-endian u64 — ties the tests' numpy model to rand.h.
+    m.def("xoshiro256pp_stream", [](uint64_t seed, uint64_t n) {
+        RandAlgoXoshiro256ppSIMD<1> rng(seed);
+        std::string out(n * 8, '\0');
+        for (uint64_t i = 0; i < n; i++) {
+            uint64_t v = rng.next();
+            std::memcpy(&out[i * 8], &v, 8);
+        }
+        return py::bytes(out);
+    }, py::arg("seed"), py::arg("n"));
+
+    // Guarded fill: preset len+guard device bytes to `sentinel`, run `calls`
+    // fills of `len` bytes on a fresh context, return all len+guard bytes so
+    // a test can compare [0,len) exactly and see any write past len.
+    // op: "checksum" (a=file_off, b=salt), "rand" (a=seed),
+    //     "blockvar" (a=seed, b=refill_len).
+    m.def("gpu_fill_guarded", [](const std::string& op, uint64_t len, uint64_t guard,
+                                 uint64_t a, uint64_t b, bool fast, int sentinel, int calls,
+                                 int dev) {
+        if (op != "checksum" && op != "rand" && op != "blockvar")
+            throw std::invalid_argument("gpu_fill_guarded: unknown op " + op);
+        const uint64_t total = len + guard;
+        GpuCtx ctx(dev, 1, total, true);
+        std::memset(ctx.hostBuf(0), sentinel, total);
+        ctx.copyH2DAsync(0, total);
+        ctx.syncStream();
+        for (int i = 0; i < calls; i++) {
+            if (op == "checksum")
+                ctx.fillChecksumDev(0, len, a, b);
+            else if (op == "rand")
+                ctx.fillRandDev(0, len, a, fast);
+            else
+                ctx.blockVarRefillDev(0, len, b, a, fast);
+        }
+        std::memset(ctx.hostBuf(0), ~sentinel, total); // D2H must overwrite all of it
+        ctx.copyD2HAsync(0, total);
+        ctx.syncStream();
+        return py::bytes(ctx.hostBuf(0), total);
+    }, py::arg("op"), py::arg("len"), py::arg("guard"), py::arg("a") = 0, py::arg("b") = 0,
+       py::arg("fast") = false, py::arg("sentinel") = 0xA5, py::arg("calls") = 1,
+       py::arg("dev") = 0);
+
+    // Batched verify: one context, one slot per (data, file_off) item, one
+    // verifyChecksumDevAsync launch each with no fetch in between; then two
+    // fetchVerifyResult calls, then (optionally) a synchronous verify of
+    // `then` on the same context. Returns the results in that order.
+    m.def("gpu_verify_batch", [](const std::vector<std::pair<py::bytes, uint64_t>>& items,
+                                 uint64_t salt, bool lds,
+                                 std::optional<std::pair<py::bytes, uint64_t>> then, int dev) {
+        std::vector<std::string> bufs;
+        uint64_t maxLen = 16;
+        for (const auto& it : items) {
+            bufs.emplace_back(it.first);
+            maxLen = std::max<uint64_t>(maxLen, bufs.back().size());
+        }
+        std::string thenBuf;
+        if (then) {
+            thenBuf = then->first;
+            maxLen = std::max<uint64_t>(maxLen, thenBuf.size());
+        }
+        if (bufs.empty()) throw std::invalid_argument("gpu_verify_batch: no items");
+        GpuCtx ctx(dev, (int)bufs.size(), maxLen, true);
+        for (size_t i = 0; i < bufs.size(); i++) {
+            std::memcpy(ctx.hostBuf((int)i), bufs[i].data(), bufs[i].size());
+            ctx.copyH2DAsync((int)i, bufs[i].size());
+            ctx.verifyChecksumDevAsync((int)i, bufs[i].size(), items[i].second, salt, lds);
+        }
+        py::list out;
+        auto push = [&](const GpuVerifyResult& r) {
+            out.append(py::make_tuple(r.numMismatches, r.firstBadFileOffset));
+        };
+        push(ctx.fetchVerifyResult());
+        push(ctx.fetchVerifyResult());
+        if (then) {
+            std::memcpy(ctx.hostBuf(0), thenBuf.data(), thenBuf.size());
+            ctx.copyH2DAsync(0, thenBuf.size());
+            ctx.syncStream();
+            push(ctx.verifyChecksumDev(0, thenBuf.size(), then->second, salt, lds));
+        }
+        return out;
+    }, py::arg("items"), py::arg("salt"), py::arg("lds") = false,
+       py::arg("then") = py::none(), py::arg("dev") = 0);
 
     m.def("gpu_verify_bench",
           [](uint64_t len, int iters, bool lds, int dev) {

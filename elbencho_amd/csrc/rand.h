@@ -146,8 +146,9 @@ private:
 // independent streams let the compiler keep N states in registers and
 // auto-vectorize the fill loop (same idea as the reference's SIMD variant;
 // fresh implementation). The GPU fill kernel in gpu_kernels.hip uses the
-// same per-stream step function, so CPU and GPU fills are testable against
-// each other.
+// same per-stream seeding and step function, so CPU and GPU fills are
+// testable against each other (tests/test_kernel_model.py ties a numpy model
+// to this class, tests/test_gpu_kernels.py ties the kernels to that model).
 template <int N>
 class RandAlgoXoshiro256ppSIMD final : public RandAlgo {
 public:

@@ -986,7 +986,9 @@ class S3Worker(threading.Thread):
     def _make_block(self, length: int, obj_off: int) -> bytes:
         cfg = self.r.cfg
         if cfg.verify >= 0:
-            if self.gpu:  # generate the pattern in HBM with the fill kernel
+            # generate the pattern in HBM with the fill kernel (whole u64
+            # words only; the kernel wrapper rejects anything else)
+            if self.gpu and obj_off % 8 == 0 and length % 8 == 0:
                 return self.gpu.fill_checksum(length, obj_off, cfg.verify)
             return self.core.fill_checksum(length, obj_off, cfg.verify)
         return bytes(self.r.rand_block[:length])
