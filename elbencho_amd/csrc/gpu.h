@@ -20,6 +20,8 @@
 #include <cstdint>
 #include <string>
 
+#include "crc.h"
+
 namespace eb {
 
 struct GpuVerifyResult {
@@ -46,6 +48,12 @@ int gpuDeviceCount();
 // lds=false runs the production LDS-free kernel, lds=true the LDS-tiled
 // variant kept only to justify that design choice.
 double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev);
+
+// Geometry of the device CRC kernel: bytes per tile (one raw partial CRC
+// each) and bytes covered by one wave within a tile. Tests key their sizes
+// off these.
+uint64_t gpuCrcTileBytes();
+uint64_t gpuCrcWaveBytes();
 
 // Diagnostic: the hipGetDeviceCount error string (or "ok: N device(s)").
 std::string gpuProbeError();
@@ -138,6 +146,27 @@ public:
     // multiple of 16 and capped at len.
     void blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint64_t seed,
                            bool fastAlgo = false);
+
+    // --- CRC-32 / CRC-32C of a slot's first len bytes, computed in HBM ---
+    // Everything these need (byte tables, the partials array) is allocated
+    // on the first call, so runs without a checksum pay nothing.
+
+    // Enqueue the tile kernel on this context's stream: one raw partial CRC
+    // per gpuCrcTileBytes() tile lands at partials[partialBase...] in a
+    // growable device array. Requires len % 16 == 0 (throws
+    // std::invalid_argument otherwise); len == 0 is a no-op. Successive
+    // calls before a fetch must use contiguous, ascending partialBase
+    // values: the calls' data, in call order, is the message.
+    void crcDevAsync(int slot, uint64_t len, CrcAlgo algo, uint64_t partialBase);
+
+    // One D2H of the partials + one stream synchronization, then the host
+    // folds them in tile order and applies init/xorout for totalLen. Returns
+    // the finished CRC of everything enqueued since the last fetch; throws
+    // std::invalid_argument if that is not totalLen bytes in tileCount tiles.
+    uint32_t crcFetch(CrcAlgo algo, uint64_t totalLen, uint64_t tileCount);
+
+    // crcDevAsync + crcFetch of one buffer. Synchronizes.
+    uint32_t crcDev(int slot, uint64_t len, CrcAlgo algo);
 
 private:
     struct Impl;

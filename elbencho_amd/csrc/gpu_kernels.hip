@@ -4,6 +4,7 @@
 // HBM3E access, grid-stride loops capped so the launch fills all 8 XCDs
 // (>=2048 workgroups for large buffers), LDS-free reductions via wave
 // ballot + per-block atomics (memory-bound ops — no MFMA-shaped work here).
+// The CRC kernel is the exception on LDS: its byte tables live there.
 //
 // Replaces the reference's CUDA runtime calls and curand usage
 // (LocalWorker.cpp:1427-1537, :2269-2310) with native CDNA4 code.
@@ -17,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "crc.h"
 #include "gpu.h"
 
 namespace eb {
@@ -351,6 +353,100 @@ __global__ __launch_bounds__(256) void ebBlockVarKernel(ulonglong2* __restrict__
     }
 }
 
+// CRC-32 / CRC-32C of a device buffer: one RAW partial (init 0, no xorout)
+// per tile, written to partial[tileIdx] — no atomics, so the result does not
+// depend on the grid. The host folds the partials in tile order (crcFetch).
+//
+// Geometry: a workgroup of CRC_WAVES_PER_TILE waves takes one tile per
+// grid-stride pass; each wave covers CRC_STEPS_PER_WAVE rows of 64 lanes x
+// 16 B, so one wave covers CRC_WAVE_BYTES and a tile CRC_TILE_BYTES.
+//
+// A CRC is not a commutative reduction: every partial result is weighted by
+// x^(8 * distance to the end) mod P. All distances here are fixed, so each
+// weight is a constant, and "multiply by a constant mod P" is four byte-table
+// lookups (gfx950 has no carry-less multiply). The tables (crc.h,
+// crcBuildTileTables; 48 KiB) are copied into LDS once per workgroup:
+//   - 16 lookups turn a lane's 16 B element into its raw CRC,
+//   - the lane's accumulator is shifted by one row between steps (Horner),
+//   - lanes are joined by __shfl_down with the shift doubling each step,
+//   - thread 0 joins the waves' results through LDS.
+// A short final tile is right-aligned in the tile's frame: the missing
+// leading elements count as zeros, which a raw CRC ignores, so the same
+// constants serve every tile and nothing past `nVec2` is read.
+constexpr int CRC_STEPS_PER_WAVE = 4; // rows of 64 x 16 B per wave and tile
+constexpr int CRC_WAVES_PER_TILE = 4; // = 256 threads / 64
+constexpr uint64_t CRC_WAVE_BYTES = (uint64_t)CRC_ROW_BYTES * CRC_STEPS_PER_WAVE; // 4 KiB
+constexpr uint64_t CRC_TILE_BYTES = CRC_WAVE_BYTES * CRC_WAVES_PER_TILE;          // 16 KiB
+
+__device__ __forceinline__ uint32_t d_crcLut4(const uint32_t* tab, uint32_t v)
+{
+    return tab[v & 0xFF] ^ tab[256 + ((v >> 8) & 0xFF)] ^ tab[512 + ((v >> 16) & 0xFF)] ^
+           tab[768 + (v >> 24)];
+}
+
+__global__ __launch_bounds__(256) void ebCrcTilesKernel(const ulonglong2* __restrict__ buf,
+                                                        uint64_t nVec2, // # of 16B elements
+                                                        const uint32_t* __restrict__ tables,
+                                                        uint32_t* __restrict__ partial)
+{
+    __shared__ uint32_t tab[CRC_TAB_COUNT * 256];
+    __shared__ uint32_t wavePart[CRC_WAVES_PER_TILE];
+
+    for (int i = threadIdx.x; i < CRC_TAB_COUNT * 256 / 4; i += 256)
+        ((uint4*)tab)[i] = ((const uint4*)tables)[i];
+    __syncthreads();
+
+    constexpr uint64_t TILE_VEC2 = CRC_TILE_BYTES / 16;
+    const uint64_t nTiles = (nVec2 + TILE_VEC2 - 1) / TILE_VEC2;
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+
+    for (uint64_t tile = blockIdx.x; tile < nTiles; tile += gridDim.x) {
+        const uint64_t first = tile * TILE_VEC2;
+        const uint64_t have = (nVec2 - first < TILE_VEC2) ? nVec2 - first : TILE_VEC2;
+        const uint64_t pad = TILE_VEC2 - have; // leading zero elements of a short tile
+
+        ulonglong2 v[CRC_STEPS_PER_WAVE];
+#pragma unroll
+        for (int j = 0; j < CRC_STEPS_PER_WAVE; j++) { // 16 B/lane coalesced reads
+            uint64_t pos = (uint64_t)(wave * CRC_STEPS_PER_WAVE + j) * 64 + lane;
+            v[j] = make_ulonglong2(0, 0);
+            if (pos >= pad) v[j] = buf[first + pos - pad];
+        }
+
+        uint32_t acc = 0;
+#pragma unroll
+        for (int j = 0; j < CRC_STEPS_PER_WAVE; j++) {
+            uint32_t r = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                r ^= tab[(CRC_TAB_ELEM + k) * 256 + ((v[j].x >> (8 * k)) & 0xFF)];
+                r ^= tab[(CRC_TAB_ELEM + 8 + k) * 256 + ((v[j].y >> (8 * k)) & 0xFF)];
+            }
+            acc = d_crcLut4(tab + CRC_TAB_ROW * 256, acc) ^ r;
+        }
+
+        // join the 64 lanes: lane l absorbs lane l+d, shifted by the 16*d
+        // bytes that follow it; only lane 0's result is used
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            uint32_t other = __shfl_down(acc, 1 << i, 64);
+            acc = d_crcLut4(tab + (CRC_TAB_LANE + 4 * i) * 256, acc) ^ other;
+        }
+
+        if (lane == 0) wavePart[wave] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int w = 0; w < CRC_WAVES_PER_TILE; w++)
+                t = d_crcLut4(tab + CRC_TAB_WAVE * 256, t) ^ wavePart[w];
+            partial[tile] = t;
+        }
+        __syncthreads(); // wavePart is rewritten in the next pass
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host wrappers
 // ---------------------------------------------------------------------------
@@ -470,6 +566,16 @@ struct GpuCtx::Impl {
     unsigned long long* verifyOutHost = nullptr; // pinned [2]
     uint64_t fillCallCounter = 0;
     bool verifyDirty = false; // device counters hold accumulated results
+
+    // CRC state, allocated by the first crcDevAsync (runs without a
+    // checksum pay nothing)
+    uint32_t* crcTabDev[2] = {nullptr, nullptr}; // per CrcAlgo, CRC_TAB_COUNT*256 words
+    CrcShift crcTileShift[2];                    // host fold: shift by one tile
+    uint32_t* crcPartDev = nullptr;              // partial[tile], growable
+    uint32_t* crcPartHost = nullptr;             // pinned mirror
+    uint64_t crcPartCap = 0;                     // in partials
+    struct CrcCall { uint64_t base, len; };
+    std::vector<CrcCall> crcPending;             // enqueued since the last fetch
 };
 
 GpuCtx::GpuCtx(int deviceId, int numSlots, uint64_t bufSize, bool pinnedHostBufs)
@@ -549,6 +655,10 @@ GpuCtx::~GpuCtx()
         if (e) (void)hipEventDestroy(e);
     if (impl->verifyOutDev) (void)hipFree(impl->verifyOutDev);
     if (impl->verifyOutHost) (void)hipHostFree(impl->verifyOutHost);
+    for (auto p : impl->crcTabDev)
+        if (p) (void)hipFree(p);
+    if (impl->crcPartDev) (void)hipFree(impl->crcPartDev);
+    if (impl->crcPartHost) (void)hipHostFree(impl->crcPartHost);
     if (impl->stream && impl->ownStream) (void)hipStreamDestroy(impl->stream);
     delete impl;
 }
@@ -751,6 +861,98 @@ void GpuCtx::blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint6
                            seed + seq * 0x9E3779B9ULL, fillConst);
     }
     HIP_CHECK(hipGetLastError());
+}
+
+// --- CRC-32 / CRC-32C in HBM ---
+
+uint64_t gpuCrcTileBytes() { return CRC_TILE_BYTES; }
+uint64_t gpuCrcWaveBytes() { return CRC_WAVE_BYTES; }
+
+void GpuCtx::crcDevAsync(int slot, uint64_t len, CrcAlgo algo, uint64_t partialBase)
+{
+    requireAligned("crcDevAsync", len, 16);
+    if (len > impl->slotStride)
+        throw std::invalid_argument("crcDevAsync: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    if (!len) return;
+    const int a = (int)algo;
+    const uint64_t tiles = (len + CRC_TILE_BYTES - 1) / CRC_TILE_BYTES;
+
+    if (!impl->crcTabDev[a]) { // first use of this algorithm: build + upload tables
+        std::vector<uint32_t> tab = crcBuildTileTables(algo, CRC_STEPS_PER_WAVE);
+        HIP_CHECK(hipMalloc(&impl->crcTabDev[a], tab.size() * sizeof(uint32_t)));
+        HIP_CHECK(hipMemcpy(impl->crcTabDev[a], tab.data(), tab.size() * sizeof(uint32_t),
+                            hipMemcpyHostToDevice));
+        impl->crcTileShift[a] = CrcShift(algo, CRC_TILE_BYTES);
+    }
+
+    if (partialBase + tiles > impl->crcPartCap) { // grow, keeping earlier partials
+        uint64_t cap = std::max<uint64_t>(4096, impl->crcPartCap * 2);
+        while (cap < partialBase + tiles) cap *= 2;
+        uint32_t* dev = nullptr;
+        uint32_t* host = nullptr;
+        HIP_CHECK(hipMalloc(&dev, cap * sizeof(uint32_t)));
+        HIP_CHECK(hipHostMalloc(&host, cap * sizeof(uint32_t), hipHostMallocDefault));
+        if (impl->crcPartDev) {
+            HIP_CHECK(hipStreamSynchronize(impl->stream)); // kernels still writing the old one
+            HIP_CHECK(hipMemcpy(dev, impl->crcPartDev, impl->crcPartCap * sizeof(uint32_t),
+                                hipMemcpyDeviceToDevice));
+            (void)hipFree(impl->crcPartDev);
+            (void)hipHostFree(impl->crcPartHost);
+        }
+        impl->crcPartDev = dev;
+        impl->crcPartHost = host;
+        impl->crcPartCap = cap;
+    }
+
+    dim3 grid = gridForBytes(tiles * 256); // one workgroup per tile, capped
+    hipLaunchKernelGGL(ebCrcTilesKernel, grid, dim3(256), 0, impl->stream,
+                       (const ulonglong2*)impl->devBufs[slot], len / 16,
+                       (const uint32_t*)impl->crcTabDev[a], impl->crcPartDev + partialBase);
+    HIP_CHECK(hipGetLastError());
+    impl->crcPending.push_back({partialBase, len});
+}
+
+uint32_t GpuCtx::crcFetch(CrcAlgo algo, uint64_t totalLen, uint64_t tileCount)
+{
+    // the calls since the last fetch must tile [0, tileCount) in order and
+    // add up to totalLen; each call's last tile may be short
+    std::vector<Impl::CrcCall> calls;
+    calls.swap(impl->crcPending);
+    uint64_t tiles = 0, bytes = 0;
+    for (const auto& c : calls) {
+        if (c.base != tiles)
+            throw std::invalid_argument("crcFetch: partials are not contiguous in call order");
+        tiles += (c.len + CRC_TILE_BYTES - 1) / CRC_TILE_BYTES;
+        bytes += c.len;
+    }
+    if (tiles != tileCount || bytes != totalLen)
+        throw std::invalid_argument("crcFetch: " + std::to_string(tileCount) + " tiles / " +
+                                    std::to_string(totalLen) + " bytes asked, " +
+                                    std::to_string(tiles) + " / " + std::to_string(bytes) +
+                                    " enqueued");
+    if (!tileCount) return crcFinishRaw(algo, 0, 0);
+
+    HIP_CHECK(hipMemcpyAsync(impl->crcPartHost, impl->crcPartDev, tileCount * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, impl->stream));
+    HIP_CHECK(hipStreamSynchronize(impl->stream));
+
+    const CrcShift& tileShift = impl->crcTileShift[(int)algo];
+    const uint32_t* part = impl->crcPartHost;
+    uint32_t raw = 0;
+    for (const auto& c : calls) {
+        const uint64_t full = c.len / CRC_TILE_BYTES;
+        for (uint64_t i = 0; i < full; i++) raw = tileShift.apply(raw) ^ *part++;
+        if (c.len % CRC_TILE_BYTES) raw = crcCombine(algo, raw, *part++, c.len % CRC_TILE_BYTES);
+    }
+    return crcFinishRaw(algo, raw, totalLen);
+}
+
+uint32_t GpuCtx::crcDev(int slot, uint64_t len, CrcAlgo algo)
+{
+    impl->crcPending.clear();
+    crcDevAsync(slot, len, algo, 0);
+    return crcFetch(algo, len, (len + CRC_TILE_BYTES - 1) / CRC_TILE_BYTES);
 }
 
 double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev)

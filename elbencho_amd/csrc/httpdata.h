@@ -32,6 +32,7 @@
 #include <tuple>
 #include <vector>
 
+#include "crc.h"
 #include "gpu.h"
 #include "rand.h"
 
@@ -271,9 +272,84 @@ public:
         return {status, std::move(rawHdrs)};
     }
 
+    // Checksum (finished CRC-32 / CRC-32C) of exactly the len bytes that
+    // put(..., len, patternOff, salt) sends, so the caller can sign an
+    // x-amz-checksum-* header without the body ever reaching Python.
+    // Pattern bodies with a device attached are generated a second time in
+    // HBM and reduced there by the CRC tile kernel: fill + CRC per chunk on
+    // the one in-order stream (so the slot ring needs no events), one fetch
+    // and therefore one synchronization per object. The stream is drained on
+    // return, so put() finds the slots free. Random bodies are randBuf
+    // repeated: its CRC is computed once per plane and extended by
+    // crcCombine, with no GPU work.
+    uint32_t bodyCrc(uint64_t len, uint64_t patternOff, int64_t salt, CrcAlgo algo)
+    {
+        uint32_t crc = 0;
+        uint64_t done = 0;
+
+        if (salt < 0) {
+            RandCrc& rc = randCrc[(int)algo];
+            if (!rc.valid) {
+                rc.full = crcUpdate(algo, 0, randBuf.data(), maxBlock);
+                rc.xp = crcShiftPoly(algo, maxBlock);
+                rc.valid = true;
+            }
+            for (; len - done >= maxBlock; done += maxBlock)
+                crc = crcCombineXp(algo, rc.xp, crc, rc.full);
+            return crcUpdate(algo, crc, randBuf.data(), len - done);
+        }
+
+        if (gpu && patternOff % 8 == 0) {
+            // same chunks as put(); a chunk the kernels cannot take (ragged
+            // length) is filled and summed on the host
+            const uint64_t chunk = std::min<uint64_t>(maxBlock, 2 << 20);
+            const int nSlots = gpu->numSlots();
+            uint64_t devLen = 0, devTiles = 0; // enqueued, not yet fetched
+            const uint64_t tileBytes = gpuCrcTileBytes();
+            auto fetch = [&] {
+                if (!devLen) return;
+                crc = crcCombine(algo, crc, gpu->crcFetch(algo, devLen, devTiles), devLen);
+                devLen = devTiles = 0;
+            };
+            int slot = 0;
+            while (done < len) {
+                uint64_t n = std::min<uint64_t>(len - done, chunk);
+                uint64_t off = patternOff + done;
+                if (n % 16 == 0 && off % 8 == 0) {
+                    gpu->fillChecksumDev(slot, n, off, (uint64_t)salt);
+                    gpu->crcDevAsync(slot, n, algo, devTiles);
+                    devLen += n;
+                    devTiles += (n + tileBytes - 1) / tileBytes;
+                    slot = (slot + 1) % nSlots;
+                } else {
+                    fetch();
+                    fillChecksumCPU(buf, n, off, (uint64_t)salt);
+                    crc = crcUpdate(algo, crc, buf, n);
+                }
+                done += n;
+            }
+            fetch();
+            return crc;
+        }
+
+        while (done < len) {
+            uint64_t n = std::min<uint64_t>(len - done, maxBlock);
+            fillChecksumCPU(buf, n, patternOff + done, (uint64_t)salt);
+            crc = crcUpdate(algo, crc, buf, n);
+            done += n;
+        }
+        return crc;
+    }
+
     void close() { closeConn(); }
 
 private:
+    struct RandCrc {
+        bool valid = false;
+        uint32_t full = 0; // CRC of randBuf[0, maxBlock)
+        uint32_t xp = 0;   // x^(8*maxBlock) mod P
+    };
+    RandCrc randCrc[2]; // per CrcAlgo
     std::string host;
     int port;
     uint64_t maxBlock;

@@ -14,6 +14,7 @@
 
 #include <fcntl.h>
 
+#include "crc.h"
 #include "engine.h"
 #include "httpdata.h"
 #include "s3srv.h"
@@ -211,40 +212,22 @@ PYBIND11_MODULE(_core, m)
     // CRC32C (Castagnoli, slice-by-8) for the S3 client's
     // x-amz-checksum-crc32c header (--s3chksumalgo CRC32C)
     m.def("crc32c", [](py::bytes data) {
-        static uint32_t table[8][256];
-        static std::once_flag once;
-        std::call_once(once, [] {
-            const uint32_t poly = 0x82F63B78u; // reflected CRC-32C
-            for (uint32_t i = 0; i < 256; i++) {
-                uint32_t c = i;
-                for (int k = 0; k < 8; k++)
-                    c = (c & 1) ? (poly ^ (c >> 1)) : (c >> 1);
-                table[0][i] = c;
-            }
-            for (uint32_t i = 0; i < 256; i++)
-                for (int s = 1; s < 8; s++)
-                    table[s][i] = table[0][table[s - 1][i] & 0xFF] ^
-                                  (table[s - 1][i] >> 8);
-        });
         std::string buf = data;
-        const unsigned char* p = (const unsigned char*)buf.data();
-        size_t n = buf.size();
-        uint32_t crc = ~0u;
-        while (n >= 8) {
-            uint64_t w;
-            memcpy(&w, p, 8);
-            w ^= crc;
-            crc = table[7][w & 0xFF] ^ table[6][(w >> 8) & 0xFF] ^
-                  table[5][(w >> 16) & 0xFF] ^ table[4][(w >> 24) & 0xFF] ^
-                  table[3][(w >> 32) & 0xFF] ^ table[2][(w >> 40) & 0xFF] ^
-                  table[1][(w >> 48) & 0xFF] ^ table[0][(w >> 56) & 0xFF];
-            p += 8;
-            n -= 8;
-        }
-        while (n--)
-            crc = table[0][(crc ^ *p++) & 0xFF] ^ (crc >> 8);
-        return (uint32_t)~crc;
+        return crcUpdate(CrcAlgo::CRC32C, 0, buf.data(), buf.size());
     });
+
+    // CRC-32 / CRC-32C host library (csrc/crc.h): algo is "CRC32" or "CRC32C"
+    m.def("crc", [](py::bytes data, const std::string& algo) {
+        CrcAlgo a = crcAlgoFromName(algo);
+        std::string buf = data;
+        py::gil_scoped_release rel;
+        return crcUpdate(a, 0, buf.data(), buf.size());
+    }, py::arg("data"), py::arg("algo"));
+    // CRC of A||B from the CRCs of A and B (zlib crc32_combine semantics)
+    m.def("crc_combine", [](const std::string& algo, uint32_t crcA, uint32_t crcB,
+                            uint64_t lenB) {
+        return crcCombine(crcAlgoFromName(algo), crcA, crcB, lenB);
+    }, py::arg("algo"), py::arg("crc_a"), py::arg("crc_b"), py::arg("len_b"));
 
     // --- offset generator test hook ---
     m.def("gen_offsets",
@@ -423,6 +406,25 @@ PYBIND11_MODULE(_core, m)
     }, py::arg("items"), py::arg("salt"), py::arg("lds") = false,
        py::arg("then") = py::none(), py::arg("dev") = 0);
 
+    // Device CRC test helper: data plus `guard` sentinel bytes go into one
+    // slot; returns the CRC the tile kernel + host fold give for len(data).
+    m.def("gpu_crc", [](py::bytes data, const std::string& algo, int dev, uint64_t guard,
+                        int sentinel) {
+        CrcAlgo a = crcAlgoFromName(algo);
+        std::string buf = data;
+        py::gil_scoped_release rel;
+        const uint64_t total = buf.size() + guard;
+        GpuCtx ctx(dev, 1, std::max<uint64_t>(total, 16), true);
+        std::memcpy(ctx.hostBuf(0), buf.data(), buf.size());
+        std::memset(ctx.hostBuf(0) + buf.size(), sentinel, guard);
+        if (total) ctx.copyH2DAsync(0, total);
+        ctx.syncStream();
+        return ctx.crcDev(0, buf.size(), a);
+    }, py::arg("data"), py::arg("algo"), py::arg("dev") = 0, py::arg("guard") = 0,
+       py::arg("sentinel") = 0);
+    m.def("gpu_crc_tile_bytes", &gpuCrcTileBytes);
+    m.def("gpu_crc_wave_bytes", &gpuCrcWaveBytes);
+
     m.def("gpu_verify_bench",
           [](uint64_t len, int iters, bool lds, int dev) {
               py::gil_scoped_release rel;
@@ -475,6 +477,8 @@ PYBIND11_MODULE(_core, m)
         d["blockvar_gbps"] = timeIt([&] { ctx.blockVarRefillDev(0, len, len / 2, 9); });
         ctx.fillChecksumDev(0, len, 0, 7);
         d["verify_gbps"] = timeIt([&] { (void)ctx.verifyChecksumDev(0, len, 0, 7); });
+        if (len % 16 == 0)
+            d["crc32c_gbps"] = timeIt([&] { (void)ctx.crcDev(0, len, CrcAlgo::CRC32C); });
         d["d2h_gbps"] = timeIt([&] { ctx.copyD2HAsync(0, len); ctx.syncStream(); });
         d["h2d_gbps"] = timeIt([&] { ctx.copyH2DAsync(0, len); ctx.syncStream(); });
         return d;
@@ -570,6 +574,15 @@ PYBIND11_MODULE(_core, m)
              },
              py::arg("request_headers"), py::arg("len"),
              py::arg("pattern_off") = 0, py::arg("salt") = -1)
+        .def("body_crc",
+             [](HttpDataPlane& h, uint64_t len, uint64_t pattern_off, int64_t salt,
+                const std::string& algo) {
+                 CrcAlgo a = crcAlgoFromName(algo);
+                 py::gil_scoped_release rel;
+                 return h.bodyCrc(len, pattern_off, salt, a);
+             },
+             py::arg("len"), py::arg("pattern_off") = 0, py::arg("salt") = -1,
+             py::arg("algo") = "CRC32C")
         .def("close", &HttpDataPlane::close);
     m.def("http_dataplane_live", [] { return HttpDataPlane::liveCount().load(); });
 

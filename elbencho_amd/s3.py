@@ -89,9 +89,12 @@ class S3Client:
     # --- native data plane (csrc/httpdata.h): block bodies in C++ ---
     def attach_native(self, dev: int, max_block: int) -> bool:
         """Route object-body transfers through the native data plane
-        (SigV4 signing stays here). Not used with HTTPS or per-block
-        checksum trailers (those need the body bytes in Python)."""
-        if self.secure or self.checksum_algo:
+        (SigV4 signing stays here). Not used with HTTPS, nor with SHA1 /
+        SHA256 checksums (those need the body bytes in Python). CRC32 and
+        CRC32C stay native: the plane computes the checksum of the body it
+        is about to generate (HttpDataPlane.body_crc — in HBM for pattern
+        bodies when a device is attached)."""
+        if self.secure or self.checksum_algo not in ("", "CRC32", "CRC32C"):
             return False
         self.native = load_core().HttpDataPlane(
             self.host, self.port, dev, max_block,
@@ -114,16 +117,25 @@ class S3Client:
                           pattern_off: int, salt: int,
                           query: dict[str, str] | None = None) -> str:
         """PUT with a natively generated body (checksum pattern when
-        salt >= 0, random otherwise). Returns the ETag."""
+        salt >= 0, random otherwise). Returns the ETag. With a CRC32 /
+        CRC32C checksum_algo the plane computes the body's checksum first
+        and it rides in the signed headers (multipart parts included)."""
         with self.lock:
+            headers = dict(self.extra_put_headers)
+            if self.checksum_algo:
+                import base64
+                import struct
+                algo = self.checksum_algo
+                crc = self.native.body_crc(length, pattern_off, salt, algo)
+                headers["x-amz-sdk-checksum-algorithm"] = algo
+                headers[f"x-amz-checksum-{algo.lower()}"] = \
+                    base64.b64encode(struct.pack(">I", crc)).decode()
             req = self._native_raw_request(
-                "PUT", f"/{bucket}/{key}", query,
-                dict(self.extra_put_headers), length)
+                "PUT", f"/{bucket}/{key}", query, dict(headers), length)
             status, raw_hdrs = self.native.put(req, length, pattern_off, salt)
             if status < 0:  # connection problem: one clean retry
                 req = self._native_raw_request(
-                    "PUT", f"/{bucket}/{key}", query,
-                    dict(self.extra_put_headers), length)
+                    "PUT", f"/{bucket}/{key}", query, dict(headers), length)
                 status, raw_hdrs = self.native.put(req, length, pattern_off,
                                                    salt)
         self._check(status if status > 0 else 599, b"",

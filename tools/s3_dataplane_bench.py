@@ -8,6 +8,7 @@ verify path on. Prints one summary line per phase.
 
 Usage: s3_dataplane_bench.py [--threads N] [--objsize S] [--block B]
                              [--objects K] [--gpu] [--verify SALT]
+                             [--chksumalgo ALGO]
 """
 
 from __future__ import annotations
@@ -32,6 +33,9 @@ def main() -> int:
     ap.add_argument("--gpu", action="store_true")
     ap.add_argument("--verify", type=int, default=-1)
     ap.add_argument("--iodepth", type=int, default=1)
+    ap.add_argument("--chksumalgo", default="",
+                    help="--s3chksumalgo for the run (CRC32/CRC32C keep the "
+                         "native plane; SHA1/SHA256 take the Python path)")
     args = ap.parse_args()
 
     core = load_core()
@@ -49,6 +53,8 @@ def main() -> int:
         base += ["--gpuids", "0"]
     if args.verify >= 0:
         base += ["--verify", str(args.verify)]
+    if args.chksumalgo:
+        base += ["--s3chksumalgo", args.chksumalgo]
 
     with tempfile.TemporaryDirectory() as td:
         jsonf = os.path.join(td, "res.json")
@@ -66,7 +72,8 @@ def main() -> int:
                       f"({bytes_total / 1024**2:.0f} MiB in {el_ms:.0f} ms, "
                       f"t={args.threads} obj={args.objsize} blk={args.block} "
                       f"qd={args.iodepth} gpu={args.gpu} "
-                      f"verify={args.verify})", flush=True)
+                      f"verify={args.verify} "
+                      f"chksum={args.chksumalgo or '-'})", flush=True)
     srv.stop()
     return 0
 
