@@ -880,6 +880,10 @@ void Worker::fileModeBlocks(bool isWrite)
                 collectHalfLat(1);
             }
         } else {
+            // a READ that threw mid-window (CPU tail check, I/O error,
+            // interrupt) leaves its unfetched mismatches in this persistent
+            // context's counters: drop them so they are not reported now
+            if (doVerify) (void)gpu->fetchVerifyResult();
             int slot = 0;
             std::vector<uint64_t> preadUs(lat ? nSlots : 0, 0);
             while (gen->next(spec)) {
@@ -1052,6 +1056,10 @@ void Worker::fileModeBlocksGpuMmap(bool isWrite)
                               "; mismatching 8-byte words: " +
                               std::to_string(r.numMismatches));
     };
+
+    // drop mismatches that a READ which threw mid-window left unfetched in
+    // this persistent context's counters (see fileModeBlocks)
+    if (doVerify && !isWrite) (void)gpu->fetchVerifyResult();
 
     const uint64_t totalBlocks = numBlocksPerFile * numFiles;
 
@@ -2873,6 +2881,30 @@ Engine::LivePoll Engine::poll()
         lp.latSumEntries += w->liveEntryLatSum.load(std::memory_order_relaxed);
     }
     return lp;
+}
+
+Engine::GpuSlotsSnapshot Engine::gpuSlots(int localRank)
+{
+    if (phaseRunning)
+        throw std::runtime_error("gpu_slots: a phase is running (call finish_phase first)");
+    if (localRank < 0) throw std::out_of_range("gpu_slots: bad worker rank");
+
+    // parked workers are idle between finishPhase and the next startPhase,
+    // so their context is safe to use from the calling thread
+    GpuCtx* ctx = nullptr;
+    if ((size_t)localRank < workers.size()) ctx = workers[localRank]->gpuCtx();
+    std::lock_guard<std::mutex> lk(gpuCacheMtx);
+    if (!ctx && (size_t)localRank < gpuCtxCache.size()) ctx = gpuCtxCache[localRank].get();
+    if (!ctx)
+        throw std::runtime_error("gpu_slots: worker " + std::to_string(localRank) +
+                                 " has no GPU context");
+
+    GpuSlotsSnapshot snap;
+    ctx->bindThread();
+    snap.numSlots = ctx->numSlots();
+    snap.slotStride = ctx->slotStride();
+    ctx->snapshotSlots(snap.bytes);
+    return snap;
 }
 
 std::vector<WorkerResult> Engine::finishPhase()

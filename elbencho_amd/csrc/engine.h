@@ -174,6 +174,10 @@ public:
     // worker is parked at the phase gate.
     void resetPhaseStats();
 
+    // this worker's GPU context (nullptr without --gpuids or before its first
+    // data phase); only for use while the worker is parked at the phase gate
+    GpuCtx* gpuCtx() const { return gpu.get(); }
+
 private:
     using Clock = std::chrono::steady_clock;
 
@@ -288,6 +292,17 @@ public:
     std::pair<uint64_t, uint64_t> plannedWork(Phase phase) const;
 
     const EngineConfig& config() const { return cfg; }
+
+    // Read-only snapshot of one worker's device slot ring (test/diagnostic
+    // hook): looks at the persistent worker's context first, then at a
+    // context parked in gpuCtxCache. Throws while a phase is running (never
+    // blocks) and when that worker has no GPU context.
+    struct GpuSlotsSnapshot {
+        int numSlots = 0;
+        uint64_t slotStride = 0;
+        std::vector<char> bytes; // numSlots * slotStride
+    };
+    GpuSlotsSnapshot gpuSlots(int localRank);
 
     // ---- shared state visible to workers ----
     EngineConfig cfg;

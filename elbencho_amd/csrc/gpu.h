@@ -19,6 +19,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "crc.h"
 
@@ -77,6 +78,15 @@ public:
     char* hostBuf(int slot) const;
     uint64_t bufSize() const { return slotSize; }
     int numSlots() const { return slots; }
+    // distance between consecutive slots in the device (and host) slab: the
+    // 4 KiB-rounded slot size
+    uint64_t slotStride() const;
+
+    // Read-only snapshot of the whole device slab (numSlots * slotStride
+    // bytes, slot i at i * slotStride) into dst, copied on this context's
+    // stream; synchronizes. Diagnostic/test hook: no I/O path calls it and it
+    // leaves device memory and the pinned host buffers untouched.
+    void snapshotSlots(std::vector<char>& dst);
 
     // bind the calling thread to this context's device (hipSetDevice);
     // required when a cached context is reused by a new worker thread

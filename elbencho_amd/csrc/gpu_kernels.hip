@@ -667,6 +667,17 @@ char* GpuCtx::hostBuf(int slot) const { return impl->hostBufs[slot]; }
 
 void GpuCtx::bindThread() { HIP_CHECK(hipSetDevice(devId)); }
 
+uint64_t GpuCtx::slotStride() const { return impl->slotStride; }
+
+void GpuCtx::snapshotSlots(std::vector<char>& dst)
+{
+    dst.resize(impl->slotStride * (uint64_t)slots);
+    if (dst.empty()) return;
+    HIP_CHECK(hipMemcpyAsync(dst.data(), impl->devBase, dst.size(), hipMemcpyDeviceToHost,
+                             impl->stream));
+    HIP_CHECK(hipStreamSynchronize(impl->stream));
+}
+
 void GpuCtx::copyFromHostAsync(int slot, const void* src, uint64_t len)
 {
     HIP_CHECK(hipMemcpyAsync(impl->devBufs[slot], src, len, hipMemcpyHostToDevice,

@@ -646,6 +646,19 @@ PYBIND11_MODULE(_core, m)
                  for (auto& r : rs) out.append(resultToDict(r));
                  return out;
              })
+        // read-only copy of worker local_rank's device slot ring:
+        // (num_slots, slot_stride, bytes); raises while a phase is running
+        .def("gpu_slots",
+             [](Engine& e, int localRank) {
+                 Engine::GpuSlotsSnapshot snap;
+                 {
+                     py::gil_scoped_release rel;
+                     snap = e.gpuSlots(localRank);
+                 }
+                 return py::make_tuple(snap.numSlots, snap.slotStride,
+                                       py::bytes(snap.bytes.data(), snap.bytes.size()));
+             },
+             py::arg("local_rank") = 0)
         .def("planned_work", [](Engine& e, int phaseCode) {
             auto pw = e.plannedWork((Phase)phaseCode);
             return py::make_tuple(pw.first, pw.second);

@@ -314,3 +314,25 @@ def test_interrupt_responsive_in_uring_paths(core, tmp_path):
     assert _time.monotonic() - t0 < 5.0
     res = eng.finish_phase()
     assert all("interrupt" in r["error"] for r in res)
+
+
+def test_gpu_slots_needs_a_gpu_context_and_an_idle_engine(core, tmp_path):
+    """Engine.gpu_slots (device slot snapshot for the GPU tests) raises
+    instead of blocking while a phase runs, and raises for a worker that has
+    no GPU context, as every worker of a CPU-only run."""
+    p = str(tmp_path / "f")
+    cfg = dict(paths=[p], path_type="file", threads=1, num_dataset_threads=1,
+               file_size=1 << 20, block_size=1 << 20)
+    eng = core.Engine(cfg)
+    eng.prepare()
+    with pytest.raises(RuntimeError, match="no GPU context"):
+        eng.gpu_slots(0)
+    eng.start_phase(core.PHASES["WRITE"])
+    with pytest.raises(RuntimeError, match="phase is running"):
+        eng.gpu_slots(0)
+    assert eng.wait_phase_done(30_000)
+    assert not [r["error"] for r in eng.finish_phase() if r["error"]]
+    with pytest.raises(RuntimeError, match="no GPU context"):
+        eng.gpu_slots(0)
+    with pytest.raises(IndexError):
+        eng.gpu_slots(-1)
