@@ -96,6 +96,11 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_argument_group("data integrity & variance")
     g.add_argument("--verify", type=int, default=-1, metavar="SALT",
                    help="Write/check offset-based block checksums with the given salt.")
+    g.add_argument("--verifymixpct", type=int, default=-1, metavar="PCT",
+                   help="With --verify: hash the checksum words in the first PCT percent of "
+                        "each block, so that this part does not compress; the data stays "
+                        "verifiable. 0..100. File, block device and directory paths only. "
+                        "(Default: unset, the plain --verify pattern)")
     g.add_argument("--verifydirect", action="store_true",
                    help="Verify each block by read-back immediately after writing.")
     g.add_argument("--readinline", action="store_true",
@@ -482,6 +487,7 @@ def args_to_config(args: argparse.Namespace) -> BenchConfig:
     cfg.sharesize = parse_size(args.sharesize)
 
     cfg.verify = args.verify
+    cfg.verify_mix_pct = args.verifymixpct
     cfg.verify_direct = args.verifydirect
     cfg.read_inline = args.readinline
     cfg.stat_inline = args.statinline
@@ -744,6 +750,30 @@ def print_topic_help(topic: str) -> None:
             fmt.add_arguments(g._group_actions)
             fmt.end_section()
             print(fmt.format_help())
+
+
+def bash_completion() -> str:
+    """The bash completion script, generated from the parser: every option
+    string completes, anything else completes as a file name. Packaging
+    installs this text as etc/bash_completion.d/elbencho-amd
+    (tools/elbencho-amd-bash-completion prints it)."""
+    opts = sorted({o for a in build_parser()._actions for o in a.option_strings})
+    return "\n".join([
+        "# bash completion for elbencho-amd (generated from the CLI parser)",
+        "_elbencho_amd()",
+        "{",
+        '  local cur="${COMP_WORDS[COMP_CWORD]}"',
+        f'  local opts="{" ".join(opts)}"',
+        '  if [[ "$cur" == -* ]]; then',
+        '    COMPREPLY=( $(compgen -W "$opts" -- "$cur") )',
+        "  else",
+        '    COMPREPLY=( $(compgen -f -- "$cur") )',
+        "  fi",
+        "}",
+        "complete -F _elbencho_amd elbencho-amd",
+        "complete -F _elbencho_amd elbencho_amd",
+        "",
+    ])
 
 
 def main(argv: list[str] | None = None) -> int:

@@ -104,6 +104,7 @@ class BenchConfig:
 
     # --- integrity / variance ---
     verify: int = -1               # --verify SALT (-1 off)
+    verify_mix_pct: int = -1       # --verifymixpct (-1 = plain --verify pattern)
     verify_direct: bool = False    # --verifydirect
     read_inline: bool = False      # --readinline
     stat_inline: bool = False      # --statinline
@@ -409,6 +410,17 @@ class BenchConfig:
                                   "file/bdev mode (--nodiocheck to skip this check)")
         if self.verify >= 0 and self.random and not self.rand_aligned:
             raise ConfigError("--verify cannot be used with unaligned random offsets")
+        if self.verify_mix_pct != -1:
+            if not (0 <= self.verify_mix_pct <= 100):
+                raise ConfigError("verifymixpct must be in 0..100")
+            if self.verify < 0:
+                raise ConfigError("--verifymixpct requires --verify")
+            if self.bench_mode in ("s3", "hdfs", "netbench"):
+                raise ConfigError("--verifymixpct supports file, block device and "
+                                  "directory paths only")
+            if self.block_size % 8:
+                raise ConfigError("--verifymixpct requires a block size that is a "
+                                  "multiple of 8")
         # reference ProgArgs.cpp:1548-1556: readback verification and inline
         # reads are sync-engine features
         if self.verify_direct and (self.verify < 0 or not self.run_write):
@@ -514,6 +526,7 @@ class BenchConfig:
             trunc_to_size=self.file_size if self.trunc_to_size else None,
             prealloc=self.prealloc,
             verify_salt=self.verify,
+            verify_mix_pct=self.verify_mix_pct,
             verify_direct=self.verify_direct,
             blockvar_pct=self.blockvar_pct,
             blockvar_algo=self.blockvar_algo,

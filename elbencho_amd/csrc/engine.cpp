@@ -98,6 +98,90 @@ uint64_t verifyChecksumCPU(const char* buf, uint64_t len, uint64_t fileOff, uint
 }
 
 // ---------------------------------------------------------------------------
+// --verifymixpct pattern (CPU side)
+// u64 at 8-aligned file offset o holds splitmix64(o + salt) if
+// (o % blockSize) < mixLen, else the plain (o + salt). blockSize and mixLen are
+// multiples of 8, so a word is never split between the two kinds.
+// ---------------------------------------------------------------------------
+
+static inline uint64_t splitmix64Of(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+static inline uint64_t mixValueAt(uint64_t alignedOff, uint64_t salt, uint64_t rel,
+                                  uint64_t mixLen)
+{
+    uint64_t x = alignedOff + salt;
+    return (rel < mixLen) ? splitmix64Of(x) : x;
+}
+
+void fillChecksumMixCPU(char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                        uint64_t blockSize, uint64_t mixLen)
+{
+    // pos/end are compared by difference only (see fillChecksumCPU); rel
+    // follows pos inside the block so the aligned loop needs no division
+    uint64_t pos = fileOff;
+    uint64_t end = fileOff + len;
+
+    while (pos != end && (pos & 7)) {
+        uint64_t a = pos & ~7ULL;
+        uint64_t v = mixValueAt(a, salt, a % blockSize, mixLen);
+        buf[pos - fileOff] = (char)((v >> (8 * (pos & 7))) & 0xff);
+        pos++;
+    }
+    uint64_t rel = pos % blockSize;
+    while (end - pos >= 8) {
+        uint64_t v = mixValueAt(pos, salt, rel, mixLen);
+        std::memcpy(buf + (pos - fileOff), &v, 8);
+        pos += 8;
+        rel += 8;
+        if (rel >= blockSize) rel = 0;
+    }
+    while (pos != end) {
+        uint64_t v = mixValueAt(pos & ~7ULL, salt, rel, mixLen);
+        buf[pos - fileOff] = (char)((v >> (8 * (pos & 7))) & 0xff);
+        pos++;
+    }
+}
+
+uint64_t verifyChecksumMixCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                              uint64_t blockSize, uint64_t mixLen)
+{
+    uint64_t pos = fileOff;
+    uint64_t end = fileOff + len;
+
+    while (pos != end && (pos & 7)) {
+        uint64_t a = pos & ~7ULL;
+        uint64_t v = mixValueAt(a, salt, a % blockSize, mixLen);
+        if (buf[pos - fileOff] != (char)((v >> (8 * (pos & 7))) & 0xff)) return pos;
+        pos++;
+    }
+    uint64_t rel = pos % blockSize;
+    while (end - pos >= 8) {
+        uint64_t v = mixValueAt(pos, salt, rel, mixLen);
+        uint64_t got;
+        std::memcpy(&got, buf + (pos - fileOff), 8);
+        if (got != v) { // find exact byte
+            for (int b = 0; b < 8; b++)
+                if (((got >> (8 * b)) & 0xff) != ((v >> (8 * b)) & 0xff)) return pos + b;
+        }
+        pos += 8;
+        rel += 8;
+        if (rel >= blockSize) rel = 0;
+    }
+    while (pos != end) {
+        uint64_t v = mixValueAt(pos & ~7ULL, salt, rel, mixLen);
+        if (buf[pos - fileOff] != (char)((v >> (8 * (pos & 7))) & 0xff)) return pos;
+        pos++;
+    }
+    return UINT64_MAX;
+}
+
+// ---------------------------------------------------------------------------
 // small helpers
 // ---------------------------------------------------------------------------
 
@@ -512,10 +596,18 @@ void Worker::preWriteFill(int slot, uint64_t len, uint64_t fileOff)
     if (cfg.verifySalt >= 0) {
         // integrity fill
         if (gpu && (fileOff % 8 == 0) && (len % 8 == 0)) {
-            gpu->fillChecksumDev(slot, len, fileOff, (uint64_t)cfg.verifySalt);
+            if (eng.verifyMix)
+                gpu->fillChecksumMixDev(slot, len, fileOff, (uint64_t)cfg.verifySalt,
+                                        cfg.blockSize, eng.verifyMixLen);
+            else
+                gpu->fillChecksumDev(slot, len, fileOff, (uint64_t)cfg.verifySalt);
             return; // D2H staging copies it to host buf
         }
-        fillChecksumCPU(buf, len, fileOff, (uint64_t)cfg.verifySalt);
+        if (eng.verifyMix)
+            fillChecksumMixCPU(buf, len, fileOff, (uint64_t)cfg.verifySalt, cfg.blockSize,
+                               eng.verifyMixLen);
+        else
+            fillChecksumCPU(buf, len, fileOff, (uint64_t)cfg.verifySalt);
         if (gpu) { // keep device buffer coherent for the D2H staging copy
             gpu->copyH2DAsync(slot, len);
             gpu->syncStream();
@@ -556,7 +648,11 @@ void Worker::postReadCheck(int slot, uint64_t len, uint64_t fileOff)
     if (cfg.verifySalt < 0) return;
 
     if (gpu && (fileOff % 8 == 0) && (len % 16 == 0)) {
-        GpuVerifyResult r = gpu->verifyChecksumDev(slot, len, fileOff, (uint64_t)cfg.verifySalt);
+        GpuVerifyResult r =
+            eng.verifyMix
+                ? gpu->verifyChecksumMixDev(slot, len, fileOff, (uint64_t)cfg.verifySalt,
+                                            cfg.blockSize, eng.verifyMixLen)
+                : gpu->verifyChecksumDev(slot, len, fileOff, (uint64_t)cfg.verifySalt);
         if (r.numMismatches)
             throw WorkerError("Data verification failed (GPU). First bad file offset: " +
                               std::to_string(r.firstBadFileOffset) +
@@ -564,7 +660,12 @@ void Worker::postReadCheck(int slot, uint64_t len, uint64_t fileOff)
         return;
     }
 
-    uint64_t bad = verifyChecksumCPU(hostBufs[slot], len, fileOff, (uint64_t)cfg.verifySalt);
+    uint64_t bad = eng.verifyMix
+                       ? verifyChecksumMixCPU(hostBufs[slot], len, fileOff,
+                                              (uint64_t)cfg.verifySalt, cfg.blockSize,
+                                              eng.verifyMixLen)
+                       : verifyChecksumCPU(hostBufs[slot], len, fileOff,
+                                           (uint64_t)cfg.verifySalt);
     if (bad != UINT64_MAX)
         throw WorkerError("Data verification failed. First bad file offset: " +
                           std::to_string(bad));
@@ -910,15 +1011,25 @@ void Worker::fileModeBlocks(bool isWrite)
                 if (lat) gpu->recordTimedEnd(slot);
                 if (doVerify) {
                     if ((inFileOff % 8 == 0) && (ioLen % 16 == 0)) {
-                        gpu->verifyChecksumDevAsync(slot, ioLen, inFileOff,
-                                                    (uint64_t)cfg.verifySalt);
+                        if (eng.verifyMix)
+                            gpu->verifyChecksumMixDevAsync(slot, ioLen, inFileOff,
+                                                           (uint64_t)cfg.verifySalt,
+                                                           cfg.blockSize, eng.verifyMixLen);
+                        else
+                            gpu->verifyChecksumDevAsync(slot, ioLen, inFileOff,
+                                                        (uint64_t)cfg.verifySalt);
                         if (++sinceFetch >= VERIFY_FETCH_INTERVAL) {
                             fetchVerify();
                             sinceFetch = 0;
                         }
                     } else { // odd tail: CPU check of the host copy
-                        uint64_t bad = verifyChecksumCPU(hostBufs[slot], ioLen, inFileOff,
-                                                         (uint64_t)cfg.verifySalt);
+                        uint64_t bad =
+                            eng.verifyMix
+                                ? verifyChecksumMixCPU(hostBufs[slot], ioLen, inFileOff,
+                                                       (uint64_t)cfg.verifySalt,
+                                                       cfg.blockSize, eng.verifyMixLen)
+                                : verifyChecksumCPU(hostBufs[slot], ioLen, inFileOff,
+                                                    (uint64_t)cfg.verifySalt);
                         if (bad != UINT64_MAX)
                             throw WorkerError(
                                 "Data verification failed. First bad file offset: " +
@@ -1111,15 +1222,25 @@ void Worker::fileModeBlocksGpuMmap(bool isWrite)
             gpu->copyFromHostAsync(slot, bases[fileIdx] + inFileOff, ioLen);
             if (lat) gpu->recordTimedEnd(slot);
             if (doVerify && (inFileOff % 8 == 0) && (ioLen % 16 == 0)) {
-                gpu->verifyChecksumDevAsync(slot, ioLen, inFileOff,
-                                            (uint64_t)cfg.verifySalt);
+                if (eng.verifyMix)
+                    gpu->verifyChecksumMixDevAsync(slot, ioLen, inFileOff,
+                                                   (uint64_t)cfg.verifySalt, cfg.blockSize,
+                                                   eng.verifyMixLen);
+                else
+                    gpu->verifyChecksumDevAsync(slot, ioLen, inFileOff,
+                                                (uint64_t)cfg.verifySalt);
                 if (++sinceFetch >= VERIFY_FETCH_INTERVAL) {
                     fetchVerify();
                     sinceFetch = 0;
                 }
             } else if (doVerify) { // odd tail: check the mapped pages directly
-                uint64_t bad = verifyChecksumCPU(bases[fileIdx] + inFileOff, ioLen,
-                                                 inFileOff, (uint64_t)cfg.verifySalt);
+                uint64_t bad =
+                    eng.verifyMix
+                        ? verifyChecksumMixCPU(bases[fileIdx] + inFileOff, ioLen, inFileOff,
+                                               (uint64_t)cfg.verifySalt, cfg.blockSize,
+                                               eng.verifyMixLen)
+                        : verifyChecksumCPU(bases[fileIdx] + inFileOff, ioLen, inFileOff,
+                                            (uint64_t)cfg.verifySalt);
                 if (bad != UINT64_MAX)
                     throw WorkerError("Data verification failed. First bad file offset: " +
                                       std::to_string(bad));
@@ -2707,7 +2828,23 @@ void Worker::threadMain()
 // Engine
 // ---------------------------------------------------------------------------
 
-Engine::Engine(EngineConfig cfgIn) : cfg(std::move(cfgIn)) {}
+Engine::Engine(EngineConfig cfgIn) : cfg(std::move(cfgIn))
+{
+    if (cfg.verifyMixPct < -1 || cfg.verifyMixPct > 100)
+        throw std::invalid_argument("verify_mix_pct must be in 0..100 (or -1 for unset)");
+    if (cfg.verifyMixPct >= 0) {
+        if (cfg.verifySalt < 0)
+            throw std::invalid_argument("verify_mix_pct requires verify_salt");
+        if (!cfg.blockSize || cfg.blockSize % 8)
+            throw std::invalid_argument(
+                "verify_mix_pct requires a block size that is a multiple of 8");
+        verifyMix = true;
+        // blockSize / 100 * pct would lose the remainder; the product can
+        // overflow only for block sizes beyond 2^57
+        verifyMixLen = (uint64_t)((unsigned __int128)cfg.blockSize * cfg.verifyMixPct / 100)
+                       & ~7ULL;
+    }
+}
 
 Engine::~Engine()
 {

@@ -58,6 +58,7 @@ struct EngineConfig {
     bool fsyncPerFile = false;
 
     int64_t verifySalt = -1; // -1 = off
+    int verifyMixPct = -1;   // --verifymixpct: -1 = plain --verify pattern
     bool verifyDirect = false;
     bool readInline = false;  // read each file back right after writing it
     bool statInline = false;  // fstat right after open in dir mode
@@ -344,6 +345,12 @@ public:
     std::vector<uint64_t> resolvedFileSizes; // per path (file/bdev mode)
     uint64_t effFileSize = 0;                // uniform stripe unit
 
+    // --verifymixpct, fixed at construction: the first verifyMixLen bytes of
+    // every block hold hashed words (floor(blockSize * pct / 100), rounded
+    // down to a multiple of 8)
+    bool verifyMix = false;
+    uint64_t verifyMixLen = 0;
+
     // GPU contexts cached across phases (hipMalloc + pinned allocs are
     // expensive; reusing them keeps phase setup off the measured path)
     std::mutex gpuCacheMtx;
@@ -382,5 +389,13 @@ private:
 void fillChecksumCPU(char* buf, uint64_t len, uint64_t fileOff, uint64_t salt);
 // returns UINT64_MAX when ok, else file offset of first mismatching byte
 uint64_t verifyChecksumCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt);
+
+// --verifymixpct variants: the u64 at 8-aligned file offset o has value
+// splitmix64(o + salt) if (o % blockSize) < mixLen, else o + salt. blockSize
+// (> 0) and mixLen are multiples of 8.
+void fillChecksumMixCPU(char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                        uint64_t blockSize, uint64_t mixLen);
+uint64_t verifyChecksumMixCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                              uint64_t blockSize, uint64_t mixLen);
 
 } // namespace eb

@@ -50,6 +50,13 @@ int gpuDeviceCount();
 // variant kept only to justify that design choice.
 double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev);
 
+// Micro-bench of the --verifymixpct kernels on one len-byte buffer (GB/s):
+// fill=false times ebVerifyChecksumMixKernel, fill=true the fill kernel
+// (plainFill: ebFillChecksumKernel instead, timed the same way for comparison).
+// Requires len % 16 == 0 and len <= blockSize.
+double gpuMixBenchGBs(uint64_t len, int iters, int dev, uint64_t blockSize, uint64_t mixLen,
+                      bool fill, bool plainFill);
+
 // Geometry of the device CRC kernel: bytes per tile (one raw partial CRC
 // each) and bytes covered by one wave within a tile. Tests key their sizes
 // off these.
@@ -149,6 +156,21 @@ public:
     // Synchronizes.
     GpuVerifyResult verifyChecksumDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
                                       bool ldsVariant = false);
+
+    // --verifymixpct variants of the three calls above. The u64 at 8-aligned
+    // file offset o holds splitmix64(o + salt) if (o % blockSize) < mixLen,
+    // else o + salt; mixLen == 0 gives the plain pattern. Same alignment
+    // contract as the plain calls; in addition blockSize % 8 == 0,
+    // mixLen % 8 == 0, mixLen <= blockSize and len <= blockSize (one launch
+    // wraps the block boundary at most once), else std::invalid_argument.
+    // The verifies add into the same persistent counters as the plain ones,
+    // so fetchVerifyResult() serves both.
+    void fillChecksumMixDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                            uint64_t blockSize, uint64_t mixLen);
+    void verifyChecksumMixDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                   uint64_t blockSize, uint64_t mixLen);
+    GpuVerifyResult verifyChecksumMixDev(int slot, uint64_t len, uint64_t fileOff,
+                                         uint64_t salt, uint64_t blockSize, uint64_t mixLen);
 
     // Block-variance refill: first refillLen bytes random, remainder filled
     // with one random u64 constant (defeats dedup). Requires len % 16 == 0

@@ -245,6 +245,98 @@ __global__ __launch_bounds__(256) void ebVerifyChecksumKernel(const ulonglong2* 
     }
 }
 
+// --verifymixpct pattern: the word at byte index i of the launch lies at
+// rel = (phase + i) mod B inside its block (phase = fileOff % B, len <= B, so
+// one conditional subtract replaces the division) and holds
+// splitmix64(fileOff + i + salt) if rel < M, else the plain fileOff + i + salt.
+__device__ __forceinline__ uint64_t d_mixWordAt(uint64_t byteIdx, uint64_t fileOff,
+                                                uint64_t salt, uint64_t phase,
+                                                uint64_t blockSize, uint64_t mixLen)
+{
+    uint64_t rel = phase + byteIdx;
+    if (rel >= blockSize) rel -= blockSize;
+    uint64_t x = fileOff + byteIdx + salt;
+    uint64_t state = x;
+    uint64_t hashed = d_splitmix64(state);
+    return (rel < mixLen) ? hashed : x;
+}
+
+// Integrity fill with a hashed (incompressible) prefix of mixLen bytes per
+// block. Same shape as ebFillChecksumKernel; the two words of one 16 B
+// element are decided separately because mixLen % 16 may be 8.
+__global__ __launch_bounds__(256) void ebFillChecksumMixKernel(uint64_t* __restrict__ buf,
+                                                               uint64_t n64,
+                                                               uint64_t fileOff,
+                                                               uint64_t salt,
+                                                               uint64_t phase,
+                                                               uint64_t blockSize,
+                                                               uint64_t mixLen)
+{
+    uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t nVec2 = n64 / 2;
+    ulonglong2* __restrict__ v = (ulonglong2*)buf;
+    for (uint64_t i = tid; i < nVec2; i += stride) {
+        ulonglong2 val;
+        val.x = d_mixWordAt(i * 16, fileOff, salt, phase, blockSize, mixLen);
+        val.y = d_mixWordAt(i * 16 + 8, fileOff, salt, phase, blockSize, mixLen);
+        v[i] = val;
+    }
+    if (tid == 0 && (n64 & 1))
+        buf[n64 - 1] = d_mixWordAt((n64 - 1) * 8, fileOff, salt, phase, blockSize, mixLen);
+}
+
+// Verify of the --verifymixpct pattern: ebVerifyChecksumKernel's reduction
+// and counters (out[0] += mismatches, out[1] = min first bad file offset).
+__global__ __launch_bounds__(256) void ebVerifyChecksumMixKernel(
+    const ulonglong2* __restrict__ buf, uint64_t n64, uint64_t fileOff, uint64_t salt,
+    uint64_t phase, uint64_t blockSize, uint64_t mixLen, unsigned long long* __restrict__ out)
+{
+    uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t nVec2 = n64 / 2;
+
+    unsigned long long localBad = 0;
+    unsigned long long localFirst = ~0ULL;
+
+    for (uint64_t i = tid; i < nVec2; i += stride) {
+        ulonglong2 v = buf[i]; // 16 B/lane coalesced read
+        uint64_t off0 = fileOff + i * 16;
+        uint64_t exp0 = d_mixWordAt(i * 16, fileOff, salt, phase, blockSize, mixLen);
+        uint64_t exp1 = d_mixWordAt(i * 16 + 8, fileOff, salt, phase, blockSize, mixLen);
+        if (v.x != exp0) {
+            localBad++;
+            if (off0 < localFirst) localFirst = off0;
+        }
+        if (v.y != exp1) {
+            localBad++;
+            if (off0 + 8 < localFirst) localFirst = off0 + 8;
+        }
+    }
+
+    if (tid == 0 && (n64 & 1)) { // odd final u64
+        uint64_t offT = fileOff + (n64 - 1) * 8;
+        if (((const uint64_t*)buf)[n64 - 1] !=
+            d_mixWordAt((n64 - 1) * 8, fileOff, salt, phase, blockSize, mixLen)) {
+            localBad++;
+            if (offT < localFirst) localFirst = offT;
+        }
+    }
+
+    // wave64 reduction: sum mismatches and min first-bad across lanes
+#pragma unroll
+    for (int delta = 32; delta > 0; delta >>= 1) {
+        localBad += __shfl_down(localBad, delta, 64);
+        unsigned long long other = __shfl_down(localFirst, delta, 64);
+        if (other < localFirst) localFirst = other;
+    }
+
+    if ((threadIdx.x & 63) == 0 && localBad) {
+        atomicAdd(&out[0], localBad);
+        atomicMin(&out[1], localFirst);
+    }
+}
+
 // LDS-tiled verify variant — kept ONLY for the A/B that justifies the
 // LDS-free design above (profiles/r02_lds_ab.md): stages 16 KiB tiles
 // through LDS before comparing. For a streaming compare the extra
@@ -845,6 +937,71 @@ GpuVerifyResult GpuCtx::verifyChecksumDev(int slot, uint64_t len, uint64_t fileO
     return fetchVerifyResult();
 }
 
+// --verifymixpct launch contract on top of requireAligned(len 8, fileOff 8):
+// one launch never spans more than one block length, so the kernels need a
+// single conditional subtract to find a word's place in its block
+static void requireMixGeometry(const char* what, uint64_t len, uint64_t blockSize,
+                               uint64_t mixLen)
+{
+    if (!blockSize || blockSize % 8)
+        throw std::invalid_argument(std::string(what) + ": block size " +
+                                    std::to_string(blockSize) +
+                                    " is not a positive multiple of 8");
+    if (mixLen % 8)
+        throw std::invalid_argument(std::string(what) + ": mix length " +
+                                    std::to_string(mixLen) + " is not a multiple of 8");
+    if (mixLen > blockSize)
+        throw std::invalid_argument(std::string(what) + ": mix length " +
+                                    std::to_string(mixLen) + " exceeds the block size " +
+                                    std::to_string(blockSize));
+    if (len > blockSize)
+        throw std::invalid_argument(std::string(what) + ": len " + std::to_string(len) +
+                                    " exceeds the block size " + std::to_string(blockSize));
+}
+
+void GpuCtx::fillChecksumMixDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                uint64_t blockSize, uint64_t mixLen)
+{
+    requireAligned("fillChecksumMixDev", len, 8, fileOff);
+    requireMixGeometry("fillChecksumMixDev", len, blockSize, mixLen);
+    if (len > impl->slotStride)
+        throw std::invalid_argument("fillChecksumMixDev: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    uint64_t n64 = len / 8;
+    if (!n64) return;
+    dim3 grid = gridForBytes(n64);
+    hipLaunchKernelGGL(ebFillChecksumMixKernel, grid, dim3(256), 0, impl->stream,
+                       (uint64_t*)impl->devBufs[slot], n64, fileOff, salt,
+                       fileOff % blockSize, blockSize, mixLen);
+    HIP_CHECK(hipGetLastError());
+}
+
+void GpuCtx::verifyChecksumMixDevAsync(int slot, uint64_t len, uint64_t fileOff,
+                                       uint64_t salt, uint64_t blockSize, uint64_t mixLen)
+{
+    requireAligned("verifyChecksumMixDev", len, 8, fileOff);
+    requireMixGeometry("verifyChecksumMixDev", len, blockSize, mixLen);
+    if (len > impl->slotStride)
+        throw std::invalid_argument("verifyChecksumMixDev: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    uint64_t n64 = len / 8;
+    if (!n64) return;
+    dim3 grid = gridForBytes(n64 / 2);
+    hipLaunchKernelGGL(ebVerifyChecksumMixKernel, grid, dim3(256), 0, impl->stream,
+                       (const ulonglong2*)impl->devBufs[slot], n64, fileOff, salt,
+                       fileOff % blockSize, blockSize, mixLen, impl->verifyOutDev);
+    HIP_CHECK(hipGetLastError());
+    impl->verifyDirty = true;
+}
+
+GpuVerifyResult GpuCtx::verifyChecksumMixDev(int slot, uint64_t len, uint64_t fileOff,
+                                             uint64_t salt, uint64_t blockSize,
+                                             uint64_t mixLen)
+{
+    verifyChecksumMixDevAsync(slot, len, fileOff, salt, blockSize, mixLen);
+    return fetchVerifyResult();
+}
+
 void GpuCtx::blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint64_t seed,
                                bool fastAlgo)
 {
@@ -993,6 +1150,62 @@ double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev)
     };
 
     launch(); // warmup
+    launch();
+    HIP_CHECK(hipStreamSynchronize(s));
+
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    HIP_CHECK(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; i++) launch();
+    HIP_CHECK(hipEventRecord(e1, s));
+    HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(buf);
+    (void)hipFree(out);
+
+    return (double)len * iters / (ms / 1000.0) / 1e9;
+}
+
+double gpuMixBenchGBs(uint64_t len, int iters, int dev, uint64_t blockSize, uint64_t mixLen,
+                      bool fill, bool plainFill)
+{
+    requireAligned("gpuMixBenchGBs", len, 16);
+    requireMixGeometry("gpuMixBenchGBs", len, blockSize, mixLen);
+    if (!len || iters < 1) throw std::invalid_argument("gpuMixBenchGBs: nothing to run");
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t n64 = len / 8;
+    ulonglong2* buf = nullptr;
+    unsigned long long* out = nullptr;
+    HIP_CHECK(hipMalloc(&buf, len));
+    HIP_CHECK(hipMalloc(&out, 2 * sizeof(unsigned long long)));
+    HIP_CHECK(hipMemset(out, 0, 2 * sizeof(unsigned long long)));
+
+    hipStream_t s;
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+
+    auto launchFill = [&] {
+        hipLaunchKernelGGL(ebFillChecksumMixKernel, gridForBytes(n64), dim3(256), 0, s,
+                           (uint64_t*)buf, n64, 0, 7, 0, blockSize, mixLen);
+    };
+    auto launch = [&] {
+        if (fill && plainFill)
+            hipLaunchKernelGGL(ebFillChecksumKernel, gridForBytes(n64), dim3(256), 0, s,
+                               (uint64_t*)buf, n64, 0, 7);
+        else if (fill)
+            launchFill();
+        else
+            hipLaunchKernelGGL(ebVerifyChecksumMixKernel, gridForBytes(n64 / 2), dim3(256), 0,
+                               s, buf, n64, 0, 7, 0, blockSize, mixLen, out);
+    };
+
+    launchFill(); // the data the verify reads (clean: no atomics in the timed loop)
+    launch();     // warmup
     launch();
     HIP_CHECK(hipStreamSynchronize(s));
 

@@ -26,6 +26,16 @@ using namespace eb;
 
 namespace {
 
+// geometry the CPU mix loops take for granted (the engine checks it once, in
+// its constructor; the GPU wrappers check it per call)
+void requireMixArgs(const char* what, uint64_t blockSize, uint64_t mixLen)
+{
+    if (!blockSize || blockSize % 8 || mixLen % 8 || mixLen > blockSize)
+        throw std::invalid_argument(std::string(what) +
+                                    ": block_size must be a positive multiple of 8 and "
+                                    "mix_len a multiple of 8 not above it");
+}
+
 EngineConfig configFromDict(const py::dict& d)
 {
     EngineConfig c;
@@ -69,6 +79,7 @@ EngineConfig configFromDict(const py::dict& d)
     c.preallocFile = getB("prealloc", false);
     c.fsyncPerFile = getB("fsync", false);
     c.verifySalt = getI("verify_salt", -1);
+    c.verifyMixPct = (int)getI("verify_mix_pct", -1);
     c.verifyDirect = getB("verify_direct", false);
     c.readInline = getB("read_inline", false);
     c.statInline = getB("stat_inline", false);
@@ -208,6 +219,23 @@ PYBIND11_MODULE(_core, m)
         std::string buf = data;
         return verifyChecksumCPU(buf.data(), buf.size(), fileOff, salt);
     });
+
+    // --verifymixpct pattern on the CPU (tests tie these to the numpy model)
+    m.def("fill_checksum_mix", [](uint64_t len, uint64_t fileOff, uint64_t salt,
+                                  uint64_t blockSize, uint64_t mixLen) {
+        requireMixArgs("fill_checksum_mix", blockSize, mixLen);
+        std::string buf(len, '\0');
+        fillChecksumMixCPU(buf.data(), len, fileOff, salt, blockSize, mixLen);
+        return py::bytes(buf);
+    }, py::arg("len"), py::arg("file_off"), py::arg("salt"), py::arg("block_size"),
+       py::arg("mix_len"));
+    m.def("verify_checksum_mix", [](py::bytes data, uint64_t fileOff, uint64_t salt,
+                                    uint64_t blockSize, uint64_t mixLen) {
+        requireMixArgs("verify_checksum_mix", blockSize, mixLen);
+        std::string buf = data;
+        return verifyChecksumMixCPU(buf.data(), buf.size(), fileOff, salt, blockSize, mixLen);
+    }, py::arg("data"), py::arg("file_off"), py::arg("salt"), py::arg("block_size"),
+       py::arg("mix_len"));
 
     // CRC32C (Castagnoli, slice-by-8) for the S3 client's
     // x-amz-checksum-crc32c header (--s3chksumalgo CRC32C)
@@ -405,6 +433,103 @@ PYBIND11_MODULE(_core, m)
         return out;
     }, py::arg("items"), py::arg("salt"), py::arg("lds") = false,
        py::arg("then") = py::none(), py::arg("dev") = 0);
+
+    // --- test-only helpers for the --verifymixpct kernels ---
+
+    // Guarded mix fill: len+guard device bytes preset to `sentinel`, one
+    // fillChecksumMixDev of len bytes, all len+guard bytes returned.
+    m.def("gpu_fill_checksum_mix", [](uint64_t len, uint64_t guard, uint64_t fileOff,
+                                      uint64_t salt, uint64_t blockSize, uint64_t mixLen,
+                                      int sentinel, int dev) {
+        const uint64_t total = len + guard;
+        GpuCtx ctx(dev, 1, std::max<uint64_t>(total, 16), true);
+        std::memset(ctx.hostBuf(0), sentinel, total);
+        if (total) ctx.copyH2DAsync(0, total);
+        ctx.syncStream();
+        ctx.fillChecksumMixDev(0, len, fileOff, salt, blockSize, mixLen);
+        std::memset(ctx.hostBuf(0), ~sentinel, total); // D2H must overwrite all of it
+        if (total) ctx.copyD2HAsync(0, total);
+        ctx.syncStream();
+        return py::bytes(ctx.hostBuf(0), total);
+    }, py::arg("len"), py::arg("guard"), py::arg("file_off"), py::arg("salt"),
+       py::arg("block_size"), py::arg("mix_len"), py::arg("sentinel") = 0xA5,
+       py::arg("dev") = 0);
+
+    m.def("gpu_verify_checksum_mix", [](py::bytes data, uint64_t fileOff, uint64_t salt,
+                                        uint64_t blockSize, uint64_t mixLen, int dev) {
+        std::string buf = data;
+        GpuCtx ctx(dev, 1, std::max<uint64_t>(buf.size(), 16), true);
+        std::memcpy(ctx.hostBuf(0), buf.data(), buf.size());
+        if (!buf.empty()) ctx.copyH2DAsync(0, buf.size());
+        ctx.syncStream();
+        GpuVerifyResult r =
+            ctx.verifyChecksumMixDev(0, buf.size(), fileOff, salt, blockSize, mixLen);
+        return py::make_tuple(r.numMismatches, r.firstBadFileOffset);
+    }, py::arg("data"), py::arg("file_off"), py::arg("salt"), py::arg("block_size"),
+       py::arg("mix_len"), py::arg("dev") = 0);
+
+    // Like gpu_verify_batch for the mix kernel: one slot and one async launch
+    // per (data, file_off) item with no fetch in between; plain_items are
+    // verified with the plain kernel on the same context, interleaved after
+    // the mix item of the same index (the rest after the last mix item).
+    // Returns the results of two fetchVerifyResult calls.
+    m.def("gpu_verify_mix_batch", [](const std::vector<std::pair<py::bytes, uint64_t>>& items,
+                                     uint64_t salt, uint64_t blockSize, uint64_t mixLen,
+                                     const std::vector<std::pair<py::bytes, uint64_t>>& plainItems,
+                                     int dev) {
+        if (items.empty()) throw std::invalid_argument("gpu_verify_mix_batch: no items");
+        std::vector<std::string> bufs, plainBufs;
+        uint64_t maxLen = 16;
+        for (const auto& it : items) bufs.emplace_back(it.first);
+        for (const auto& it : plainItems) plainBufs.emplace_back(it.first);
+        for (const auto& b : bufs) maxLen = std::max<uint64_t>(maxLen, b.size());
+        for (const auto& b : plainBufs) maxLen = std::max<uint64_t>(maxLen, b.size());
+        GpuCtx ctx(dev, (int)(bufs.size() + plainBufs.size()), maxLen, true);
+        int slot = 0;
+        auto stage = [&](const std::string& b) {
+            std::memcpy(ctx.hostBuf(slot), b.data(), b.size());
+            if (!b.empty()) ctx.copyH2DAsync(slot, b.size());
+        };
+        auto plainAt = [&](size_t i) {
+            stage(plainBufs[i]);
+            ctx.verifyChecksumDevAsync(slot++, plainBufs[i].size(), plainItems[i].second, salt);
+        };
+        for (size_t i = 0; i < bufs.size(); i++) {
+            stage(bufs[i]);
+            ctx.verifyChecksumMixDevAsync(slot++, bufs[i].size(), items[i].second, salt,
+                                          blockSize, mixLen);
+            if (i < plainBufs.size()) plainAt(i);
+        }
+        for (size_t i = bufs.size(); i < plainBufs.size(); i++) plainAt(i);
+        py::list out;
+        for (int k = 0; k < 2; k++) {
+            GpuVerifyResult r = ctx.fetchVerifyResult();
+            out.append(py::make_tuple(r.numMismatches, r.firstBadFileOffset));
+        }
+        return out;
+    }, py::arg("items"), py::arg("salt"), py::arg("block_size"), py::arg("mix_len"),
+       py::arg("plain_items") = std::vector<std::pair<py::bytes, uint64_t>>{},
+       py::arg("dev") = 0);
+
+    // block_size 0 stands for len (one launch never exceeds a block)
+    m.def("gpu_verify_mix_bench",
+          [](uint64_t len, int iters, int dev, uint64_t blockSize, uint64_t mixLen) {
+              py::gil_scoped_release rel;
+              return gpuMixBenchGBs(len, iters, dev, blockSize ? blockSize : len, mixLen,
+                                    false, false);
+          },
+          py::arg("len"), py::arg("iters") = 50, py::arg("dev") = 0,
+          py::arg("block_size") = 0, py::arg("mix_len") = 0);
+    // plain=true times ebFillChecksumKernel the same way, for comparison
+    m.def("gpu_fill_mix_bench",
+          [](uint64_t len, int iters, int dev, uint64_t blockSize, uint64_t mixLen,
+             bool plain) {
+              py::gil_scoped_release rel;
+              return gpuMixBenchGBs(len, iters, dev, blockSize ? blockSize : len, mixLen,
+                                    true, plain);
+          },
+          py::arg("len"), py::arg("iters") = 50, py::arg("dev") = 0,
+          py::arg("block_size") = 0, py::arg("mix_len") = 0, py::arg("plain") = false);
 
     // Device CRC test helper: data plus `guard` sentinel bytes go into one
     // slot; returns the CRC the tile kernel + host fold give for len(data).
