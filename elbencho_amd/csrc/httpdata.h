@@ -82,9 +82,27 @@ public:
     HttpDataPlane& operator=(const HttpDataPlane&) = delete;
 
     // GET: returns {status, bytesReceived, numMismatches, firstBadOffset}.
-    // salt >= 0 verifies the checksum pattern at patternOff; mismatches are
-    // counted, firstBad = UINT64_MAX when clean. status -1 = connection
-    // error (caller retries). Body larger than expectLen is an error (-2).
+    // status -1 = connection error (caller retries). Body larger than
+    // expectLen is an error (-2). Only a 2xx body with salt >= 0 is verified,
+    // against the checksum pattern at patternOff; otherwise the result is
+    // {.., 0, UINT64_MAX}.
+    //
+    // What numMismatches and firstBadOffset mean (tests/
+    // test_s3_dataplane_exact.py holds the code to exactly this rule): the
+    // body is cut into chunks of C bytes, the last one shorter, with
+    // C = min(maxBlock, 2 MiB) when a device is attached and C = maxBlock
+    // otherwise (maxBlock is at least 4096).
+    //   - A chunk is checked on the GPU iff a device is attached,
+    //     patternOff % 8 == 0, the chunk's pattern offset is a multiple of 8
+    //     and its length is a multiple of 16. It contributes the number of
+    //     its mismatching u64 words and the pattern offset of the first such
+    //     word.
+    //   - Any other chunk is checked on the host. If it has a mismatch it
+    //     contributes 1 and the pattern offset of its first bad byte.
+    // numMismatches is the sum over the chunks, firstBadOffset the numeric
+    // minimum (UINT64_MAX when clean). Pattern offsets are taken mod 2^64.
+    // Every call starts from zero: mismatches that an aborted request (-1)
+    // had already found are dropped with it.
     std::tuple<int, uint64_t, uint64_t, uint64_t> get(const std::string& rawReq,
                                                       uint64_t expectLen,
                                                       uint64_t patternOff,
@@ -128,7 +146,12 @@ public:
                 ssize_t r = recvSome(dst + have, want - have);
                 if (r <= 0) {
                     closeConn();
-                    return {-1, got + have, nbad, firstBad};
+                    // the caller retries on this plane: leave no copy in
+                    // flight on the slots and no mismatch of this request
+                    // in the context's persistent verify counters
+                    if (gpuStage) gpu->syncStream();
+                    if (asyncVerifyUsed) (void)gpu->fetchVerifyResult();
+                    return {-1, got + have, 0, ~0ULL};
                 }
                 have += (uint64_t)r;
             }
@@ -213,7 +236,10 @@ public:
             std::vector<char> gpuPrepped(nSlots, 0);
 
             auto prepChunk = [&](int s, uint64_t off, uint64_t n) {
-                if (n % 8) { // odd tail: CPU-fill at send time
+                // what the fill kernel does not take (ragged length, or a
+                // chunk that starts inside a word because maxBlock % 8 != 0)
+                // is CPU-filled at send time, as in bodyCrc()
+                if (n % 8 || off % 8) {
                     gpuPrepped[s] = 0;
                     return;
                 }
