@@ -334,7 +334,13 @@ void Worker::checkInterrupt()
 void Worker::allocBuffers()
 {
     if (!hostBufs.empty()) { // persistent worker: buffers survive phases
-        if (gpu) gpu->bindThread();
+        if (gpu) {
+            gpu->bindThread();
+            // a --lat phase that threw before its drain (verify failure, I/O
+            // error, interrupt) left timed pairs uncollected in this
+            // persistent context: they are not this phase's samples
+            gpu->dropTimedPairs();
+        }
         return;
     }
 

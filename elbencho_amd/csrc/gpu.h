@@ -128,6 +128,9 @@ public:
     // synchronize on the slot's end event, return elapsed microseconds and
     // clear the pair
     uint64_t timedElapsedUSec(int slot);
+    // forget pairs that were recorded but never collected (a phase that
+    // threw before its drain), so the next phase does not count them
+    void dropTimedPairs();
 
     // async verify accumulating into persistent device counters; results
     // fetched (and reset) by fetchVerifyResult() — lets the caller batch

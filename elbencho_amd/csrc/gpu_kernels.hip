@@ -850,6 +850,11 @@ uint64_t GpuCtx::timedElapsedUSec(int slot)
     return (uint64_t)(ms * 1000.0f);
 }
 
+void GpuCtx::dropTimedPairs()
+{
+    for (auto& a : impl->timedActive) a = 0;
+}
+
 static void requireAligned(const char* what, uint64_t len, uint64_t lenAlign,
                            uint64_t fileOff = 0)
 {
