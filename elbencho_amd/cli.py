@@ -101,6 +101,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "each block, so that this part does not compress; the data stays "
                         "verifiable. 0..100. File, block device and directory paths only. "
                         "(Default: unset, the plain --verify pattern)")
+    g.add_argument("--verifydiag", action="store_true",
+                   help="With --verify: when a read fails verification, classify the bad "
+                        "8-byte words (zeroed, valid pattern of another offset or salt, "
+                        "flipped bits, other) and add the result to the error message. "
+                        "File, block device and directory paths only.")
     g.add_argument("--verifydirect", action="store_true",
                    help="Verify each block by read-back immediately after writing.")
     g.add_argument("--readinline", action="store_true",
@@ -488,6 +493,7 @@ def args_to_config(args: argparse.Namespace) -> BenchConfig:
 
     cfg.verify = args.verify
     cfg.verify_mix_pct = args.verifymixpct
+    cfg.verify_diag = args.verifydiag
     cfg.verify_direct = args.verifydirect
     cfg.read_inline = args.readinline
     cfg.stat_inline = args.statinline

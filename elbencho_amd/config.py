@@ -105,6 +105,7 @@ class BenchConfig:
     # --- integrity / variance ---
     verify: int = -1               # --verify SALT (-1 off)
     verify_mix_pct: int = -1       # --verifymixpct (-1 = plain --verify pattern)
+    verify_diag: bool = False      # --verifydiag (classify verify mismatches)
     verify_direct: bool = False    # --verifydirect
     read_inline: bool = False      # --readinline
     stat_inline: bool = False      # --statinline
@@ -421,6 +422,12 @@ class BenchConfig:
             if self.block_size % 8:
                 raise ConfigError("--verifymixpct requires a block size that is a "
                                   "multiple of 8")
+        if self.verify_diag:
+            if self.verify < 0:
+                raise ConfigError("--verifydiag requires --verify")
+            if self.bench_mode in ("s3", "hdfs", "netbench"):
+                raise ConfigError("--verifydiag supports file, block device and "
+                                  "directory paths only")
         # reference ProgArgs.cpp:1548-1556: readback verification and inline
         # reads are sync-engine features
         if self.verify_direct and (self.verify < 0 or not self.run_write):
@@ -527,6 +534,7 @@ class BenchConfig:
             prealloc=self.prealloc,
             verify_salt=self.verify,
             verify_mix_pct=self.verify_mix_pct,
+            verify_diag=self.verify_diag,
             verify_direct=self.verify_direct,
             blockvar_pct=self.blockvar_pct,
             blockvar_algo=self.blockvar_algo,

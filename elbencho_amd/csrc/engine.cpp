@@ -182,6 +182,155 @@ uint64_t verifyChecksumMixCPU(const char* buf, uint64_t len, uint64_t fileOff, u
 }
 
 // ---------------------------------------------------------------------------
+// --verifydiag (CPU side): the classification of GpuVerifyDiag (gpu.h), word
+// for word what ebVerifyDiagKernel / ebVerifyDiagMixKernel compute for an
+// 8-aligned range. Unaligned ranges exist only here: the bytes of a word that
+// the range holds in part are compared as the plain verify compares them, and
+// such a word, when bad, counts as OTHER at the file offset of its first byte
+// inside the range (its value cannot be decoded); pairs are counted from the
+// first whole word.
+// ---------------------------------------------------------------------------
+
+static inline uint64_t unmix64(uint64_t z) // inverse of splitmix64Of's finalizer
+{
+    z ^= (z >> 31) ^ (z >> 62);
+    z *= 0x319642B2D24D8EC3ULL;
+    z ^= (z >> 27) ^ (z >> 54);
+    z *= 0x96DE1B173F119089ULL;
+    z ^= (z >> 30) ^ (z >> 60);
+    return z;
+}
+
+static inline void diagCount(GpuVerifyDiag& a, uint64_t v, uint64_t exp, uint64_t off,
+                             bool pairPattern, int64_t d, bool runStart)
+{
+    a.numMismatches++;
+    if (off < a.firstBadFileOffset) a.firstBadFileOffset = off;
+    if (off > a.lastBadFileOffset) a.lastBadFileOffset = off;
+    if (runStart) a.runs++;
+    if (v == 0) {
+        a.zero++;
+    } else if (pairPattern) {
+        a.pattern++;
+        if (d < a.deltaMin) a.deltaMin = d;
+        if (d > a.deltaMax) a.deltaMax = d;
+    } else if (__builtin_popcountll(v ^ exp) <= 2) {
+        a.bitflip++;
+        a.flipOr |= v ^ exp;
+    } else {
+        a.other++;
+    }
+}
+
+// blockSize == 0 selects the plain pattern
+static void verifyDiagRange(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                            uint64_t blockSize, uint64_t mixLen, GpuVerifyDiag& acc)
+{
+    const bool mix = blockSize != 0;
+    uint64_t pos = fileOff; // wraps past 2^64 like the fill and verify loops
+    uint64_t left = len;
+    bool prevBad = false; // the word before pos is bad (false at the range start)
+
+    // bytes [pos, pos+n) of the word at (pos & ~7): a part of one word
+    auto partialWord = [&](uint64_t n) {
+        const uint64_t a = pos & ~7ULL;
+        const uint64_t exp = mix ? mixValueAt(a, salt, a % blockSize, mixLen) : a + salt;
+        bool bad = false;
+        for (uint64_t k = 0; k < n; k++) {
+            const uint64_t p = pos + k;
+            if (buf[p - fileOff] != (char)((exp >> (8 * (p & 7))) & 0xff)) bad = true;
+        }
+        if (bad) {
+            acc.numMismatches++;
+            if (pos < acc.firstBadFileOffset) acc.firstBadFileOffset = pos;
+            if (pos > acc.lastBadFileOffset) acc.lastBadFileOffset = pos;
+            if (!prevBad) acc.runs++;
+            acc.other++;
+        }
+        prevBad = bad;
+        pos += n;
+        left -= n;
+    };
+
+    if (left && (pos & 7)) partialWord(std::min<uint64_t>(8 - (pos & 7), left));
+
+    uint64_t rel = mix ? pos % blockSize : 0;
+    auto nextRel = [&](uint64_t r) { return (r + 8 >= blockSize) ? r + 8 - blockSize : r + 8; };
+
+    while (left >= 8) {
+        const bool have1 = left >= 16;
+        const uint64_t rel1 = mix ? nextRel(rel) : 0;
+        const uint64_t x0 = pos + salt, x1 = pos + 8 + salt;
+        const bool hashed0 = mix && rel < mixLen, hashed1 = mix && rel1 < mixLen;
+        const uint64_t exp0 = hashed0 ? splitmix64Of(x0) : x0;
+        const uint64_t exp1 = hashed1 ? splitmix64Of(x1) : x1;
+        uint64_t v0, v1 = exp1;
+        std::memcpy(&v0, buf + (pos - fileOff), 8);
+        if (have1) std::memcpy(&v1, buf + (pos - fileOff) + 8, 8);
+        const bool bad0 = v0 != exp0, bad1 = v1 != exp1;
+
+        if (bad0 || bad1) {
+            int64_t d0 = 0, d1 = 0;
+            bool pairPattern = false;
+            if (bad0 && bad1 && v0 && v1) {
+                d0 = (int64_t)((hashed0 ? unmix64(v0) - 0x9E3779B97F4A7C15ULL : v0) - x0);
+                d1 = (int64_t)((hashed1 ? unmix64(v1) - 0x9E3779B97F4A7C15ULL : v1) - x1);
+                pairPattern = d0 == d1;
+            }
+            if (bad0) diagCount(acc, v0, exp0, pos, pairPattern, d0, !prevBad);
+            if (bad1) diagCount(acc, v1, exp1, pos + 8, pairPattern, d1, !bad0);
+        }
+
+        if (have1) {
+            prevBad = bad1;
+            pos += 16;
+            left -= 16;
+            if (mix) rel = nextRel(rel1);
+        } else {
+            prevBad = bad0;
+            pos += 8;
+            left -= 8;
+        }
+    }
+
+    if (left) partialWord(left);
+}
+
+void verifyDiagCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                   GpuVerifyDiag& acc)
+{
+    verifyDiagRange(buf, len, fileOff, salt, 0, 0, acc);
+}
+
+void verifyDiagMixCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                      uint64_t blockSize, uint64_t mixLen, GpuVerifyDiag& acc)
+{
+    if (!blockSize || blockSize % 8 || mixLen % 8)
+        throw std::invalid_argument("verifyDiagMixCPU: block size and mix length must be "
+                                    "multiples of 8, the block size positive");
+    verifyDiagRange(buf, len, fileOff, salt, blockSize, mixLen, acc);
+}
+
+std::string verifyDiagText(const GpuVerifyDiag& d)
+{
+    std::string s = "; diagnosis: last bad file offset: " + std::to_string(d.lastBadFileOffset) +
+                    "; runs: " + std::to_string(d.runs) + "; zero: " + std::to_string(d.zero) +
+                    "; pattern: " + std::to_string(d.pattern) +
+                    "; bitflip: " + std::to_string(d.bitflip) +
+                    "; other: " + std::to_string(d.other);
+    if (d.pattern) {
+        s += "; pattern delta: " + std::to_string(d.deltaMin);
+        if (d.deltaMin != d.deltaMax) s += ".." + std::to_string(d.deltaMax);
+    }
+    if (d.bitflip) {
+        char hex[32];
+        snprintf(hex, sizeof(hex), "0x%llx", (unsigned long long)d.flipOr);
+        s += std::string("; flipped bits: ") + hex;
+    }
+    return s;
+}
+
+// ---------------------------------------------------------------------------
 // small helpers
 // ---------------------------------------------------------------------------
 
@@ -654,27 +803,90 @@ void Worker::postReadCheck(int slot, uint64_t len, uint64_t fileOff)
     if (cfg.verifySalt < 0) return;
 
     if (gpu && (fileOff % 8 == 0) && (len % 16 == 0)) {
-        GpuVerifyResult r =
-            eng.verifyMix
-                ? gpu->verifyChecksumMixDev(slot, len, fileOff, (uint64_t)cfg.verifySalt,
-                                            cfg.blockSize, eng.verifyMixLen)
-                : gpu->verifyChecksumDev(slot, len, fileOff, (uint64_t)cfg.verifySalt);
-        if (r.numMismatches)
-            throw WorkerError("Data verification failed (GPU). First bad file offset: " +
-                              std::to_string(r.firstBadFileOffset) +
-                              "; mismatching 8-byte words: " + std::to_string(r.numMismatches));
+        gpuVerifyAsync(slot, len, fileOff);
+        gpuVerifyFetch();
         return;
     }
 
+    cpuVerify(hostBufs[slot], len, fileOff);
+}
+
+// The three verify steps of every read path, in their plain, --verifymixpct
+// and --verifydiag forms. gpuVerifyAsync enqueues one block's verify on the
+// worker's stream; gpuVerifyFetch collects what accumulated since the last
+// fetch and throws on a mismatch; cpuVerify checks a host buffer at once.
+
+void Worker::gpuVerifyAsync(int slot, uint64_t len, uint64_t fileOff)
+{
+    const auto& cfg = eng.cfg;
+    const uint64_t salt = (uint64_t)cfg.verifySalt;
+    if (cfg.verifyDiag) {
+        if (eng.verifyMix)
+            gpu->verifyDiagMixDevAsync(slot, len, fileOff, salt, cfg.blockSize,
+                                       eng.verifyMixLen);
+        else
+            gpu->verifyDiagDevAsync(slot, len, fileOff, salt);
+    } else if (eng.verifyMix) {
+        gpu->verifyChecksumMixDevAsync(slot, len, fileOff, salt, cfg.blockSize,
+                                       eng.verifyMixLen);
+    } else {
+        gpu->verifyChecksumDevAsync(slot, len, fileOff, salt);
+    }
+}
+
+void Worker::gpuVerifyFetch()
+{
+    uint64_t numBad, firstBad;
+    std::string diagnosis;
+    if (eng.cfg.verifyDiag) {
+        GpuVerifyDiag d = gpu->fetchVerifyDiag();
+        numBad = d.numMismatches;
+        firstBad = d.firstBadFileOffset;
+        if (numBad) diagnosis = verifyDiagText(d);
+    } else {
+        GpuVerifyResult r = gpu->fetchVerifyResult();
+        numBad = r.numMismatches;
+        firstBad = r.firstBadFileOffset;
+    }
+    if (numBad)
+        throw WorkerError("Data verification failed (GPU). First bad file offset: " +
+                          std::to_string(firstBad) + "; mismatching 8-byte words: " +
+                          std::to_string(numBad) + diagnosis);
+}
+
+// drop what a READ that threw mid-window left unfetched in this persistent
+// context's counters, so it is not reported by the next phase
+void Worker::gpuVerifyDropStale()
+{
+    (void)gpu->fetchVerifyResult();
+    if (eng.cfg.verifyDiag) (void)gpu->fetchVerifyDiag();
+}
+
+void Worker::cpuVerify(const char* buf, uint64_t len, uint64_t fileOff)
+{
+    const auto& cfg = eng.cfg;
+    const uint64_t salt = (uint64_t)cfg.verifySalt;
+    std::string diagnosis;
+    if (cfg.verifyDiag) {
+        GpuVerifyDiag d;
+        if (eng.verifyMix)
+            verifyDiagMixCPU(buf, len, fileOff, salt, cfg.blockSize, eng.verifyMixLen, d);
+        else
+            verifyDiagCPU(buf, len, fileOff, salt, d);
+        if (!d.numMismatches) return;
+        // the failure path: the plain verify below finds the exact first bad
+        // byte, so the text up to the diagnosis is what a run without
+        // --verifydiag prints
+        diagnosis = "; mismatching 8-byte words: " + std::to_string(d.numMismatches) +
+                    verifyDiagText(d);
+    }
     uint64_t bad = eng.verifyMix
-                       ? verifyChecksumMixCPU(hostBufs[slot], len, fileOff,
-                                              (uint64_t)cfg.verifySalt, cfg.blockSize,
+                       ? verifyChecksumMixCPU(buf, len, fileOff, salt, cfg.blockSize,
                                               eng.verifyMixLen)
-                       : verifyChecksumCPU(hostBufs[slot], len, fileOff,
-                                           (uint64_t)cfg.verifySalt);
+                       : verifyChecksumCPU(buf, len, fileOff, salt);
     if (bad != UINT64_MAX)
         throw WorkerError("Data verification failed. First bad file offset: " +
-                          std::to_string(bad));
+                          std::to_string(bad) + diagnosis);
 }
 
 // ---------------------------------------------------------------------------
@@ -842,14 +1054,7 @@ void Worker::fileModeBlocks(bool isWrite)
         BlockSpec spec;
         uint64_t opCount = 0;
 
-        auto fetchVerify = [&]() {
-            GpuVerifyResult r = gpu->fetchVerifyResult();
-            if (r.numMismatches)
-                throw WorkerError(
-                    "Data verification failed (GPU). First bad file offset: " +
-                    std::to_string(r.firstBadFileOffset) + "; mismatching 8-byte words: " +
-                    std::to_string(r.numMismatches));
-        };
+        auto fetchVerify = [&]() { gpuVerifyFetch(); };
 
         if (isWrite) {
             // one-block lookahead: prepare (fill + D2H) next while pwriting cur
@@ -990,7 +1195,7 @@ void Worker::fileModeBlocks(bool isWrite)
             // a READ that threw mid-window (CPU tail check, I/O error,
             // interrupt) leaves its unfetched mismatches in this persistent
             // context's counters: drop them so they are not reported now
-            if (doVerify) (void)gpu->fetchVerifyResult();
+            if (doVerify) gpuVerifyDropStale();
             int slot = 0;
             std::vector<uint64_t> preadUs(lat ? nSlots : 0, 0);
             while (gen->next(spec)) {
@@ -1017,29 +1222,13 @@ void Worker::fileModeBlocks(bool isWrite)
                 if (lat) gpu->recordTimedEnd(slot);
                 if (doVerify) {
                     if ((inFileOff % 8 == 0) && (ioLen % 16 == 0)) {
-                        if (eng.verifyMix)
-                            gpu->verifyChecksumMixDevAsync(slot, ioLen, inFileOff,
-                                                           (uint64_t)cfg.verifySalt,
-                                                           cfg.blockSize, eng.verifyMixLen);
-                        else
-                            gpu->verifyChecksumDevAsync(slot, ioLen, inFileOff,
-                                                        (uint64_t)cfg.verifySalt);
+                        gpuVerifyAsync(slot, ioLen, inFileOff);
                         if (++sinceFetch >= VERIFY_FETCH_INTERVAL) {
                             fetchVerify();
                             sinceFetch = 0;
                         }
                     } else { // odd tail: CPU check of the host copy
-                        uint64_t bad =
-                            eng.verifyMix
-                                ? verifyChecksumMixCPU(hostBufs[slot], ioLen, inFileOff,
-                                                       (uint64_t)cfg.verifySalt,
-                                                       cfg.blockSize, eng.verifyMixLen)
-                                : verifyChecksumCPU(hostBufs[slot], ioLen, inFileOff,
-                                                    (uint64_t)cfg.verifySalt);
-                        if (bad != UINT64_MAX)
-                            throw WorkerError(
-                                "Data verification failed. First bad file offset: " +
-                                std::to_string(bad));
+                        cpuVerify(hostBufs[slot], ioLen, inFileOff);
                     }
                 }
                 gpu->recordSlotEvent(slot);
@@ -1165,18 +1354,11 @@ void Worker::fileModeBlocksGpuMmap(bool isWrite)
     uint64_t opCount = 0;
     int slot = 0;
 
-    auto fetchVerify = [&]() {
-        GpuVerifyResult r = gpu->fetchVerifyResult();
-        if (r.numMismatches)
-            throw WorkerError("Data verification failed (GPU). First bad file offset: " +
-                              std::to_string(r.firstBadFileOffset) +
-                              "; mismatching 8-byte words: " +
-                              std::to_string(r.numMismatches));
-    };
+    auto fetchVerify = [&]() { gpuVerifyFetch(); };
 
     // drop mismatches that a READ which threw mid-window left unfetched in
     // this persistent context's counters (see fileModeBlocks)
-    if (doVerify && !isWrite) (void)gpu->fetchVerifyResult();
+    if (doVerify && !isWrite) gpuVerifyDropStale();
 
     const uint64_t totalBlocks = numBlocksPerFile * numFiles;
 
@@ -1228,28 +1410,13 @@ void Worker::fileModeBlocksGpuMmap(bool isWrite)
             gpu->copyFromHostAsync(slot, bases[fileIdx] + inFileOff, ioLen);
             if (lat) gpu->recordTimedEnd(slot);
             if (doVerify && (inFileOff % 8 == 0) && (ioLen % 16 == 0)) {
-                if (eng.verifyMix)
-                    gpu->verifyChecksumMixDevAsync(slot, ioLen, inFileOff,
-                                                   (uint64_t)cfg.verifySalt, cfg.blockSize,
-                                                   eng.verifyMixLen);
-                else
-                    gpu->verifyChecksumDevAsync(slot, ioLen, inFileOff,
-                                                (uint64_t)cfg.verifySalt);
+                gpuVerifyAsync(slot, ioLen, inFileOff);
                 if (++sinceFetch >= VERIFY_FETCH_INTERVAL) {
                     fetchVerify();
                     sinceFetch = 0;
                 }
             } else if (doVerify) { // odd tail: check the mapped pages directly
-                uint64_t bad =
-                    eng.verifyMix
-                        ? verifyChecksumMixCPU(bases[fileIdx] + inFileOff, ioLen, inFileOff,
-                                               (uint64_t)cfg.verifySalt, cfg.blockSize,
-                                               eng.verifyMixLen)
-                        : verifyChecksumCPU(bases[fileIdx] + inFileOff, ioLen, inFileOff,
-                                            (uint64_t)cfg.verifySalt);
-                if (bad != UINT64_MAX)
-                    throw WorkerError("Data verification failed. First bad file offset: " +
-                                      std::to_string(bad));
+                cpuVerify(bases[fileIdx] + inFileOff, ioLen, inFileOff);
             }
         }
 

@@ -59,6 +59,7 @@ struct EngineConfig {
 
     int64_t verifySalt = -1; // -1 = off
     int verifyMixPct = -1;   // --verifymixpct: -1 = plain --verify pattern
+    bool verifyDiag = false; // --verifydiag: classify what a verify failure found
     bool verifyDirect = false;
     bool readInline = false;  // read each file back right after writing it
     bool statInline = false;  // fstat right after open in dir mode
@@ -242,6 +243,11 @@ private:
     }
     void preWriteFill(int slot, uint64_t len, uint64_t fileOff);
     void postReadCheck(int slot, uint64_t len, uint64_t fileOff);
+    // verify steps shared by the read paths (plain, --verifymixpct, --verifydiag)
+    void gpuVerifyAsync(int slot, uint64_t len, uint64_t fileOff);
+    void gpuVerifyFetch();     // throws WorkerError on a mismatch
+    void gpuVerifyDropStale(); // forget what a failed phase left unfetched
+    void cpuVerify(const char* buf, uint64_t len, uint64_t fileOff);
     ssize_t blockIO(bool isWrite, int fd, int slot, uint64_t len, uint64_t fileOff,
                     char* mmapBase = nullptr, const std::string* path = nullptr);
     void verifyDirectReadback(int fd, int slot, uint64_t len, uint64_t fileOff);
@@ -397,5 +403,16 @@ void fillChecksumMixCPU(char* buf, uint64_t len, uint64_t fileOff, uint64_t salt
                         uint64_t blockSize, uint64_t mixLen);
 uint64_t verifyChecksumMixCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
                               uint64_t blockSize, uint64_t mixLen);
+
+
+// --verifydiag on a host buffer: the contract of GpuVerifyDiag (gpu.h), added
+// into `acc` (a default-constructed record is empty). Any alignment; a word
+// the range holds only in part is compared on those bytes and counts as OTHER.
+void verifyDiagCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                   GpuVerifyDiag& acc);
+void verifyDiagMixCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
+                      uint64_t blockSize, uint64_t mixLen, GpuVerifyDiag& acc);
+// what a failed verify appends to its message: "; diagnosis: ..."
+std::string verifyDiagText(const GpuVerifyDiag& d);
 
 } // namespace eb

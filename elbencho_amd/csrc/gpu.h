@@ -18,6 +18,7 @@
 #pragma once
 
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -28,6 +29,25 @@ namespace eb {
 struct GpuVerifyResult {
     uint64_t numMismatches;
     uint64_t firstBadFileOffset; // UINT64_MAX if none
+};
+
+// --verifydiag record: what a verify pass saw, classified per bad word.
+// Accumulates over launches like the two counters above; the defaults are the
+// empty record. Classes, first match wins: ZERO (word reads 0), PATTERN (both
+// words of a 16-byte pair are bad, non-zero and decode to the same delta from
+// the expected offset + salt), BITFLIP (at most two bits differ), OTHER.
+// See docs/usage.md (--verifydiag) for the full contract.
+struct GpuVerifyDiag {
+    uint64_t numMismatches = 0;
+    uint64_t firstBadFileOffset = UINT64_MAX;
+    uint64_t lastBadFileOffset = 0;
+    uint64_t runs = 0; // maximal stretches of consecutive bad words, per launch
+    uint64_t zero = 0, pattern = 0, bitflip = 0, other = 0;
+    int64_t deltaMin = std::numeric_limits<int64_t>::max(); // over PATTERN words
+    int64_t deltaMax = std::numeric_limits<int64_t>::min();
+    uint64_t flipOr = 0; // OR of (found ^ expected) over BITFLIP words
+
+    static constexpr int NUM_FIELDS = 11; // device layout: the fields in this order
 };
 
 // Pin (hipHostRegister) / unpin an arbitrary host region — used to register
@@ -56,6 +76,9 @@ double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev);
 // Requires len % 16 == 0 and len <= blockSize.
 double gpuMixBenchGBs(uint64_t len, int iters, int dev, uint64_t blockSize, uint64_t mixLen,
                       bool fill, bool plainFill);
+
+// gpuVerifyBenchGBs for ebVerifyDiagKernel: same buffer, same clean data.
+double gpuVerifyDiagBenchGBs(uint64_t len, int iters, int dev);
 
 // Geometry of the device CRC kernel: bytes per tile (one raw partial CRC
 // each) and bytes covered by one wave within a tile. Tests key their sizes
@@ -175,6 +198,20 @@ public:
     GpuVerifyResult verifyChecksumMixDev(int slot, uint64_t len, uint64_t fileOff,
                                          uint64_t salt, uint64_t blockSize, uint64_t mixLen);
 
+    // --verifydiag variants of the verifies: same compare and same alignment
+    // contracts (so numMismatches / firstBadFileOffset equal the plain calls'
+    // results), plus the per-word classification of GpuVerifyDiag. They
+    // accumulate into a device record of their own, allocated on first use;
+    // fetchVerifyDiag() returns and resets it (no device work when nothing
+    // was launched since the last fetch).
+    void verifyDiagDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt);
+    void verifyDiagMixDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                               uint64_t blockSize, uint64_t mixLen);
+    GpuVerifyDiag fetchVerifyDiag();
+    GpuVerifyDiag verifyDiagDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt);
+    GpuVerifyDiag verifyDiagMixDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                   uint64_t blockSize, uint64_t mixLen);
+
     // Block-variance refill: first refillLen bytes random, remainder filled
     // with one random u64 constant (defeats dedup). Requires len % 16 == 0
     // (throws std::invalid_argument otherwise); refillLen is floored to a
@@ -206,6 +243,7 @@ public:
 private:
     struct Impl;
     Impl* impl;
+    unsigned long long* diagRecordDev(); // device record, allocated on first use
     int devId;
     uint64_t slotSize;
     int slots;

@@ -337,6 +337,203 @@ __global__ __launch_bounds__(256) void ebVerifyChecksumMixKernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// --verifydiag: the verify compare plus a classification of every bad word
+// ---------------------------------------------------------------------------
+
+// Inverse of the splitmix64 finalizer used by d_splitmix64: each xor-shift
+// z ^= z >> s is undone by z ^= z >> s ^ z >> 2s (3s >= 64 here), each
+// multiply by the modular inverse of its odd constant.
+__device__ __forceinline__ uint64_t d_unmix64(uint64_t z)
+{
+    z ^= (z >> 31) ^ (z >> 62);
+    z *= 0x319642B2D24D8EC3ULL;
+    z ^= (z >> 27) ^ (z >> 54);
+    z *= 0x96DE1B173F119089ULL;
+    z ^= (z >> 30) ^ (z >> 60);
+    return z;
+}
+
+// per-thread GpuVerifyDiag accumulators, in the record's field order
+struct DiagAcc {
+    unsigned long long nbad = 0, first = ~0ULL, last = 0, runs = 0;
+    unsigned long long zero = 0, pattern = 0, bitflip = 0, other = 0;
+    long long dmin = 0x7FFFFFFFFFFFFFFFLL, dmax = -0x7FFFFFFFFFFFFFFFLL - 1;
+    unsigned long long flipOr = 0;
+};
+
+// geometry of one diag launch; MIX=false ignores the block fields
+struct DiagGeom {
+    uint64_t fileOff, salt, phase, blockSize, mixLen;
+};
+
+template <bool MIX>
+__device__ __forceinline__ bool d_diagHashed(const DiagGeom& g, uint64_t byteIdx)
+{
+    if (!MIX) return false;
+    uint64_t rel = g.phase + byteIdx;
+    if (rel >= g.blockSize) rel -= g.blockSize;
+    return rel < g.mixLen;
+}
+
+template <bool MIX>
+__device__ __forceinline__ uint64_t d_diagExp(const DiagGeom& g, uint64_t byteIdx)
+{
+    if (MIX) return d_mixWordAt(byteIdx, g.fileOff, g.salt, g.phase, g.blockSize, g.mixLen);
+    return g.fileOff + byteIdx + g.salt;
+}
+
+// delta of a bad word: what the found value decodes to (a hashed position is
+// un-hashed first) minus the plain offset + salt expected here
+template <bool MIX>
+__device__ __forceinline__ long long d_diagDelta(const DiagGeom& g, uint64_t byteIdx,
+                                                 uint64_t v)
+{
+    uint64_t u = d_diagHashed<MIX>(g, byteIdx) ? d_unmix64(v) - 0x9E3779B97F4A7C15ULL : v;
+    return (long long)(u - (g.fileOff + byteIdx + g.salt));
+}
+
+// one bad word into the accumulators; first matching class wins
+__device__ __forceinline__ void d_diagCount(DiagAcc& a, uint64_t v, uint64_t exp,
+                                            uint64_t off, bool pairPattern, long long d,
+                                            bool runStart)
+{
+    a.nbad++;
+    if (off < a.first) a.first = off;
+    if (off > a.last) a.last = off;
+    if (runStart) a.runs++;
+    if (v == 0) {
+        a.zero++;
+    } else if (pairPattern) {
+        a.pattern++;
+        if (d < a.dmin) a.dmin = d;
+        if (d > a.dmax) a.dmax = d;
+    } else if (__popcll(v ^ exp) <= 2) {
+        a.bitflip++;
+        a.flipOr |= v ^ exp;
+    } else {
+        a.other++;
+    }
+}
+
+// Shape of ebVerifyChecksumKernel: 16 B/lane loads, grid-stride, the odd
+// final word on thread 0. A clean element costs the load and two compares
+// (the ballot below is the second compare's lane mask); everything else sits
+// behind the "this word is bad" branch.
+//
+// A bad word starts a run iff its predecessor is good. .y follows .x in the
+// same lane; .x follows the previous lane's .y, which the ballot carries.
+// Lane 0 of a wave has no previous lane and reads word 2i-1 from memory, only
+// when its .x is bad. A wave's 64 elements are consecutive (the grid stride
+// is a multiple of 256), so the rule holds in every grid-stride pass.
+template <bool MIX>
+__device__ __forceinline__ void d_verifyDiag(const ulonglong2* __restrict__ buf, uint64_t n64,
+                                             const DiagGeom g,
+                                             unsigned long long* __restrict__ out)
+{
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t nVec2 = n64 / 2;
+    const int lane = threadIdx.x & 63;
+    const uint64_t* __restrict__ words = (const uint64_t*)buf;
+
+    DiagAcc a;
+
+    for (uint64_t i = tid; i < nVec2; i += stride) {
+        ulonglong2 v = buf[i]; // 16 B/lane coalesced read
+        const uint64_t exp0 = d_diagExp<MIX>(g, i * 16);
+        const uint64_t exp1 = d_diagExp<MIX>(g, i * 16 + 8);
+        const bool badX = v.x != exp0;
+        const bool badY = v.y != exp1;
+        const unsigned long long badYMask = __ballot(badY);
+        if (badX || badY) {
+            const uint64_t off0 = g.fileOff + i * 16;
+            long long d0 = 0, d1 = 0;
+            bool pairPattern = false;
+            if (badX && badY && v.x && v.y) {
+                d0 = d_diagDelta<MIX>(g, i * 16, v.x);
+                d1 = d_diagDelta<MIX>(g, i * 16 + 8, v.y);
+                pairPattern = d0 == d1;
+            }
+            if (badX) {
+                bool prevBad = false;
+                if (lane)
+                    prevBad = (badYMask >> (lane - 1)) & 1;
+                else if (i)
+                    prevBad = words[2 * i - 1] != d_diagExp<MIX>(g, i * 16 - 8);
+                d_diagCount(a, v.x, exp0, off0, pairPattern, d0, !prevBad);
+            }
+            if (badY) d_diagCount(a, v.y, exp1, off0 + 8, pairPattern, d1, !badX);
+        }
+    }
+
+    if (tid == 0 && (n64 & 1)) { // odd final u64: no partner, predecessor n64-2
+        const uint64_t w = n64 - 1;
+        const uint64_t vT = words[w];
+        const uint64_t expT = d_diagExp<MIX>(g, w * 8);
+        if (vT != expT) {
+            bool prevBad = w && words[w - 1] != d_diagExp<MIX>(g, w * 8 - 8);
+            d_diagCount(a, vT, expT, g.fileOff + w * 8, false, 0, !prevBad);
+        }
+    }
+
+    // a clean wave is done here: no reduction, no atomics
+    if (!__ballot(a.nbad != 0)) return;
+
+#pragma unroll
+    for (int delta = 32; delta > 0; delta >>= 1) {
+        a.nbad += __shfl_down(a.nbad, delta, 64);
+        a.runs += __shfl_down(a.runs, delta, 64);
+        a.zero += __shfl_down(a.zero, delta, 64);
+        a.pattern += __shfl_down(a.pattern, delta, 64);
+        a.bitflip += __shfl_down(a.bitflip, delta, 64);
+        a.other += __shfl_down(a.other, delta, 64);
+        a.flipOr |= __shfl_down(a.flipOr, delta, 64);
+        unsigned long long oFirst = __shfl_down(a.first, delta, 64);
+        if (oFirst < a.first) a.first = oFirst;
+        unsigned long long oLast = __shfl_down(a.last, delta, 64);
+        if (oLast > a.last) a.last = oLast;
+        long long oMin = __shfl_down(a.dmin, delta, 64);
+        if (oMin < a.dmin) a.dmin = oMin;
+        long long oMax = __shfl_down(a.dmax, delta, 64);
+        if (oMax > a.dmax) a.dmax = oMax;
+    }
+
+    if (lane == 0) {
+        atomicAdd(&out[0], a.nbad);
+        atomicMin(&out[1], a.first);
+        atomicMax(&out[2], a.last);
+        atomicAdd(&out[3], a.runs);
+        if (a.zero) atomicAdd(&out[4], a.zero);
+        if (a.pattern) {
+            atomicAdd(&out[5], a.pattern);
+            atomicMin((long long*)&out[8], a.dmin);
+            atomicMax((long long*)&out[9], a.dmax);
+        }
+        if (a.bitflip) {
+            atomicAdd(&out[6], a.bitflip);
+            atomicOr(&out[10], a.flipOr);
+        }
+        if (a.other) atomicAdd(&out[7], a.other);
+    }
+}
+
+// out[] is the GpuVerifyDiag record (GpuVerifyDiag::NUM_FIELDS words).
+__global__ __launch_bounds__(256) void ebVerifyDiagKernel(const ulonglong2* __restrict__ buf,
+                                                          uint64_t n64, uint64_t fileOff,
+                                                          uint64_t salt,
+                                                          unsigned long long* __restrict__ out)
+{
+    d_verifyDiag<false>(buf, n64, DiagGeom{fileOff, salt, 0, 0, 0}, out);
+}
+
+__global__ __launch_bounds__(256) void ebVerifyDiagMixKernel(
+    const ulonglong2* __restrict__ buf, uint64_t n64, uint64_t fileOff, uint64_t salt,
+    uint64_t phase, uint64_t blockSize, uint64_t mixLen, unsigned long long* __restrict__ out)
+{
+    d_verifyDiag<true>(buf, n64, DiagGeom{fileOff, salt, phase, blockSize, mixLen}, out);
+}
+
 // LDS-tiled verify variant — kept ONLY for the A/B that justifies the
 // LDS-free design above (profiles/r02_lds_ab.md): stages 16 KiB tiles
 // through LDS before comparing. For a streaming compare the extra
@@ -659,6 +856,11 @@ struct GpuCtx::Impl {
     uint64_t fillCallCounter = 0;
     bool verifyDirty = false; // device counters hold accumulated results
 
+    // --verifydiag record, allocated by the first diag launch
+    unsigned long long* diagDev = nullptr;  // [GpuVerifyDiag::NUM_FIELDS]
+    unsigned long long* diagHost = nullptr; // pinned mirror
+    bool diagDirty = false;
+
     // CRC state, allocated by the first crcDevAsync (runs without a
     // checksum pay nothing)
     uint32_t* crcTabDev[2] = {nullptr, nullptr}; // per CrcAlgo, CRC_TAB_COUNT*256 words
@@ -747,6 +949,8 @@ GpuCtx::~GpuCtx()
         if (e) (void)hipEventDestroy(e);
     if (impl->verifyOutDev) (void)hipFree(impl->verifyOutDev);
     if (impl->verifyOutHost) (void)hipHostFree(impl->verifyOutHost);
+    if (impl->diagDev) (void)hipFree(impl->diagDev);
+    if (impl->diagHost) (void)hipHostFree(impl->diagHost);
     for (auto p : impl->crcTabDev)
         if (p) (void)hipFree(p);
     if (impl->crcPartDev) (void)hipFree(impl->crcPartDev);
@@ -1007,6 +1211,109 @@ GpuVerifyResult GpuCtx::verifyChecksumMixDev(int slot, uint64_t len, uint64_t fi
     return fetchVerifyResult();
 }
 
+// --- --verifydiag ---
+
+// the empty record in device layout (GpuVerifyDiag's field order)
+static void diagInitWords(unsigned long long* w)
+{
+    const GpuVerifyDiag init;
+    w[0] = init.numMismatches;
+    w[1] = init.firstBadFileOffset;
+    w[2] = init.lastBadFileOffset;
+    w[3] = init.runs;
+    w[4] = init.zero;
+    w[5] = init.pattern;
+    w[6] = init.bitflip;
+    w[7] = init.other;
+    w[8] = (unsigned long long)init.deltaMin;
+    w[9] = (unsigned long long)init.deltaMax;
+    w[10] = init.flipOr;
+}
+
+unsigned long long* GpuCtx::diagRecordDev()
+{
+    if (!impl->diagDev) { // first diag launch of this context
+        constexpr size_t bytes = GpuVerifyDiag::NUM_FIELDS * sizeof(unsigned long long);
+        HIP_CHECK(hipMalloc(&impl->diagDev, bytes));
+        HIP_CHECK(hipHostMalloc(&impl->diagHost, bytes, hipHostMallocDefault));
+        diagInitWords(impl->diagHost);
+        HIP_CHECK(hipMemcpy(impl->diagDev, impl->diagHost, bytes, hipMemcpyHostToDevice));
+    }
+    return impl->diagDev;
+}
+
+void GpuCtx::verifyDiagDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt)
+{
+    requireAligned("verifyDiagDev", len, 8, fileOff);
+    if (len > impl->slotStride)
+        throw std::invalid_argument("verifyDiagDev: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    uint64_t n64 = len / 8;
+    if (!n64) return;
+    unsigned long long* rec = diagRecordDev();
+    hipLaunchKernelGGL(ebVerifyDiagKernel, gridForBytes(n64 / 2), dim3(256), 0, impl->stream,
+                       (const ulonglong2*)impl->devBufs[slot], n64, fileOff, salt, rec);
+    HIP_CHECK(hipGetLastError());
+    impl->diagDirty = true;
+}
+
+void GpuCtx::verifyDiagMixDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                   uint64_t blockSize, uint64_t mixLen)
+{
+    requireAligned("verifyDiagMixDev", len, 8, fileOff);
+    requireMixGeometry("verifyDiagMixDev", len, blockSize, mixLen);
+    if (len > impl->slotStride)
+        throw std::invalid_argument("verifyDiagMixDev: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    uint64_t n64 = len / 8;
+    if (!n64) return;
+    unsigned long long* rec = diagRecordDev();
+    hipLaunchKernelGGL(ebVerifyDiagMixKernel, gridForBytes(n64 / 2), dim3(256), 0,
+                       impl->stream, (const ulonglong2*)impl->devBufs[slot], n64, fileOff,
+                       salt, fileOff % blockSize, blockSize, mixLen, rec);
+    HIP_CHECK(hipGetLastError());
+    impl->diagDirty = true;
+}
+
+GpuVerifyDiag GpuCtx::fetchVerifyDiag()
+{
+    GpuVerifyDiag r;
+    if (!impl->diagDirty) return r;
+    constexpr size_t bytes = GpuVerifyDiag::NUM_FIELDS * sizeof(unsigned long long);
+    unsigned long long* h = impl->diagHost;
+    HIP_CHECK(hipMemcpyAsync(h, impl->diagDev, bytes, hipMemcpyDeviceToHost, impl->stream));
+    HIP_CHECK(hipStreamSynchronize(impl->stream));
+    r.numMismatches = h[0];
+    r.firstBadFileOffset = h[1];
+    r.lastBadFileOffset = h[2];
+    r.runs = h[3];
+    r.zero = h[4];
+    r.pattern = h[5];
+    r.bitflip = h[6];
+    r.other = h[7];
+    r.deltaMin = (int64_t)h[8];
+    r.deltaMax = (int64_t)h[9];
+    r.flipOr = h[10];
+    diagInitWords(h);
+    HIP_CHECK(hipMemcpyAsync(impl->diagDev, h, bytes, hipMemcpyHostToDevice, impl->stream));
+    HIP_CHECK(hipStreamSynchronize(impl->stream));
+    impl->diagDirty = false;
+    return r;
+}
+
+GpuVerifyDiag GpuCtx::verifyDiagDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt)
+{
+    verifyDiagDevAsync(slot, len, fileOff, salt);
+    return fetchVerifyDiag();
+}
+
+GpuVerifyDiag GpuCtx::verifyDiagMixDev(int slot, uint64_t len, uint64_t fileOff, uint64_t salt,
+                                       uint64_t blockSize, uint64_t mixLen)
+{
+    verifyDiagMixDevAsync(slot, len, fileOff, salt, blockSize, mixLen);
+    return fetchVerifyDiag();
+}
+
 void GpuCtx::blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint64_t seed,
                                bool fastAlgo)
 {
@@ -1152,6 +1459,54 @@ double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev)
         else
             hipLaunchKernelGGL(ebVerifyChecksumKernel, grid, dim3(256), 0, s,
                                buf, n64, 0, 7, out);
+    };
+
+    launch(); // warmup
+    launch();
+    HIP_CHECK(hipStreamSynchronize(s));
+
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    HIP_CHECK(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; i++) launch();
+    HIP_CHECK(hipEventRecord(e1, s));
+    HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(buf);
+    (void)hipFree(out);
+
+    return (double)len * iters / (ms / 1000.0) / 1e9;
+}
+
+double gpuVerifyDiagBenchGBs(uint64_t len, int iters, int dev)
+{
+    requireAligned("gpuVerifyDiagBenchGBs", len, 16);
+    if (!len || iters < 1) throw std::invalid_argument("gpuVerifyDiagBenchGBs: nothing to run");
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t n64 = len / 8;
+    ulonglong2* buf = nullptr;
+    unsigned long long* out = nullptr;
+    unsigned long long init[GpuVerifyDiag::NUM_FIELDS];
+    diagInitWords(init);
+    HIP_CHECK(hipMalloc(&buf, len));
+    HIP_CHECK(hipMalloc(&out, sizeof(init)));
+    HIP_CHECK(hipMemcpy(out, init, sizeof(init), hipMemcpyHostToDevice));
+
+    hipStream_t s;
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    dim3 grid = gridForBytes(n64 / 2);
+
+    // clean data, as in gpuVerifyBenchGBs: no atomics in the timed loop
+    hipLaunchKernelGGL(ebFillChecksumKernel, gridForBytes(n64), dim3(256), 0, s,
+                       (uint64_t*)buf, n64, 0, 7);
+    auto launch = [&] {
+        hipLaunchKernelGGL(ebVerifyDiagKernel, grid, dim3(256), 0, s, buf, n64, 0, 7, out);
     };
 
     launch(); // warmup

@@ -36,6 +36,24 @@ void requireMixArgs(const char* what, uint64_t blockSize, uint64_t mixLen)
                                     "mix_len a multiple of 8 not above it");
 }
 
+// a GpuVerifyDiag as a dict keyed by the record's field names
+py::dict diagToDict(const GpuVerifyDiag& r)
+{
+    py::dict d;
+    d["nbad"] = r.numMismatches;
+    d["first"] = r.firstBadFileOffset;
+    d["last"] = r.lastBadFileOffset;
+    d["runs"] = r.runs;
+    d["zero"] = r.zero;
+    d["pattern"] = r.pattern;
+    d["bitflip"] = r.bitflip;
+    d["other"] = r.other;
+    d["delta_min"] = r.deltaMin;
+    d["delta_max"] = r.deltaMax;
+    d["flip_or"] = r.flipOr;
+    return d;
+}
+
 EngineConfig configFromDict(const py::dict& d)
 {
     EngineConfig c;
@@ -80,6 +98,7 @@ EngineConfig configFromDict(const py::dict& d)
     c.fsyncPerFile = getB("fsync", false);
     c.verifySalt = getI("verify_salt", -1);
     c.verifyMixPct = (int)getI("verify_mix_pct", -1);
+    c.verifyDiag = getB("verify_diag", false);
     c.verifyDirect = getB("verify_direct", false);
     c.readInline = getB("read_inline", false);
     c.statInline = getB("stat_inline", false);
@@ -236,6 +255,36 @@ PYBIND11_MODULE(_core, m)
         return verifyChecksumMixCPU(buf.data(), buf.size(), fileOff, salt, blockSize, mixLen);
     }, py::arg("data"), py::arg("file_off"), py::arg("salt"), py::arg("block_size"),
        py::arg("mix_len"));
+
+    // --verifydiag on the CPU; block_size 0 selects the plain pattern
+    m.def("verify_diag", [](py::bytes data, uint64_t fileOff, uint64_t salt,
+                            uint64_t blockSize, uint64_t mixLen) {
+        std::string buf = data;
+        GpuVerifyDiag r;
+        if (blockSize) {
+            requireMixArgs("verify_diag", blockSize, mixLen);
+            verifyDiagMixCPU(buf.data(), buf.size(), fileOff, salt, blockSize, mixLen, r);
+        } else {
+            verifyDiagCPU(buf.data(), buf.size(), fileOff, salt, r);
+        }
+        return diagToDict(r);
+    }, py::arg("data"), py::arg("file_off"), py::arg("salt"), py::arg("block_size") = 0,
+       py::arg("mix_len") = 0);
+    m.def("verify_diag_text", [](const py::dict& d) {
+        GpuVerifyDiag r;
+        r.numMismatches = d["nbad"].cast<uint64_t>();
+        r.firstBadFileOffset = d["first"].cast<uint64_t>();
+        r.lastBadFileOffset = d["last"].cast<uint64_t>();
+        r.runs = d["runs"].cast<uint64_t>();
+        r.zero = d["zero"].cast<uint64_t>();
+        r.pattern = d["pattern"].cast<uint64_t>();
+        r.bitflip = d["bitflip"].cast<uint64_t>();
+        r.other = d["other"].cast<uint64_t>();
+        r.deltaMin = d["delta_min"].cast<int64_t>();
+        r.deltaMax = d["delta_max"].cast<int64_t>();
+        r.flipOr = d["flip_or"].cast<uint64_t>();
+        return verifyDiagText(r);
+    }, py::arg("record"));
 
     // CRC32C (Castagnoli, slice-by-8) for the S3 client's
     // x-amz-checksum-crc32c header (--s3chksumalgo CRC32C)
@@ -510,6 +559,78 @@ PYBIND11_MODULE(_core, m)
     }, py::arg("items"), py::arg("salt"), py::arg("block_size"), py::arg("mix_len"),
        py::arg("plain_items") = std::vector<std::pair<py::bytes, uint64_t>>{},
        py::arg("dev") = 0);
+
+    // --- --verifydiag kernels; block_size 0 selects the plain kernel ---
+
+    m.def("gpu_verify_diag", [](py::bytes data, uint64_t fileOff, uint64_t salt, int dev,
+                                uint64_t blockSize, uint64_t mixLen) {
+        std::string buf = data;
+        GpuCtx ctx(dev, 1, std::max<uint64_t>(buf.size(), 16), true);
+        std::memcpy(ctx.hostBuf(0), buf.data(), buf.size());
+        if (!buf.empty()) ctx.copyH2DAsync(0, buf.size());
+        ctx.syncStream();
+        return diagToDict(blockSize ? ctx.verifyDiagMixDev(0, buf.size(), fileOff, salt,
+                                                           blockSize, mixLen)
+                                    : ctx.verifyDiagDev(0, buf.size(), fileOff, salt));
+    }, py::arg("data"), py::arg("file_off"), py::arg("salt"), py::arg("dev") = 0,
+       py::arg("block_size") = 0, py::arg("mix_len") = 0);
+
+    // Like gpu_verify_batch: one slot and one async diag launch per
+    // (data, file_off) item with no fetch in between, then two
+    // fetchVerifyDiag calls, then (optionally) a synchronous diag of `then`
+    // on the same context. Returns the records in that order. fetch_each
+    // fetches after every item instead and returns one record per item (many
+    // one-shot diagnoses on one context).
+    m.def("gpu_verify_diag_batch", [](const std::vector<std::pair<py::bytes, uint64_t>>& items,
+                                      uint64_t salt, int dev, uint64_t blockSize,
+                                      uint64_t mixLen,
+                                      std::optional<std::pair<py::bytes, uint64_t>> then,
+                                      bool fetchEach) {
+        if (items.empty()) throw std::invalid_argument("gpu_verify_diag_batch: no items");
+        std::vector<std::string> bufs;
+        uint64_t maxLen = 16;
+        for (const auto& it : items) {
+            bufs.emplace_back(it.first);
+            maxLen = std::max<uint64_t>(maxLen, bufs.back().size());
+        }
+        std::string thenBuf;
+        if (then) {
+            thenBuf = then->first;
+            maxLen = std::max<uint64_t>(maxLen, thenBuf.size());
+        }
+        GpuCtx ctx(dev, (int)bufs.size(), maxLen, true);
+        auto launch = [&](int slot, const std::string& b, uint64_t fileOff) {
+            std::memcpy(ctx.hostBuf(slot), b.data(), b.size());
+            if (!b.empty()) ctx.copyH2DAsync(slot, b.size());
+            if (blockSize)
+                ctx.verifyDiagMixDevAsync(slot, b.size(), fileOff, salt, blockSize, mixLen);
+            else
+                ctx.verifyDiagDevAsync(slot, b.size(), fileOff, salt);
+        };
+        py::list out;
+        for (size_t i = 0; i < bufs.size(); i++) {
+            launch((int)i, bufs[i], items[i].second);
+            if (fetchEach) out.append(diagToDict(ctx.fetchVerifyDiag()));
+        }
+        if (!fetchEach) {
+            out.append(diagToDict(ctx.fetchVerifyDiag()));
+            out.append(diagToDict(ctx.fetchVerifyDiag()));
+        }
+        if (then) {
+            launch(0, thenBuf, then->second);
+            out.append(diagToDict(ctx.fetchVerifyDiag()));
+        }
+        return out;
+    }, py::arg("items"), py::arg("salt"), py::arg("dev") = 0, py::arg("block_size") = 0,
+       py::arg("mix_len") = 0, py::arg("then") = py::none(), py::arg("fetch_each") = false);
+
+    // like gpu_verify_bench (clean data, GB/s) for ebVerifyDiagKernel
+    m.def("gpu_verify_diag_bench",
+          [](uint64_t len, int iters, int dev) {
+              py::gil_scoped_release rel;
+              return gpuVerifyDiagBenchGBs(len, iters, dev);
+          },
+          py::arg("len"), py::arg("iters") = 50, py::arg("dev") = 0);
 
     // block_size 0 stands for len (one launch never exceeds a block)
     m.def("gpu_verify_mix_bench",
