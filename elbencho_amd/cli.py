@@ -377,11 +377,13 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--s3sessiontoken", default="", metavar="TOKEN",
                    help="S3 session token (x-amz-security-token header).")
     g.add_argument("--s3chksumalgo", default="", metavar="ALGO",
-                   help="S3 checksum algorithm (CRC32, CRC32C, SHA1, SHA256): sets the "
-                        "x-amz-sdk-checksum-algorithm and x-amz-checksum-* headers on "
-                        "uploads. CRC32 and CRC32C keep the native data plane (the "
-                        "checksum of generated bodies is computed there, on the GPU "
-                        "with --gpuids); SHA1 and SHA256 use the Python client.")
+                   help="S3 checksum algorithm (CRC32, CRC32C, CRC64NVME, SHA1, SHA256): "
+                        "sets the x-amz-sdk-checksum-algorithm and x-amz-checksum-* "
+                        "headers on uploads. CRC32, CRC32C and CRC64NVME keep the native "
+                        "data plane (the checksum of generated bodies is computed there, "
+                        "on the GPU with --gpuids); SHA1 and SHA256 use the Python "
+                        "client. With CRC64NVME multipart uploads are initiated as "
+                        "FULL_OBJECT checksum uploads.")
     g.add_argument("--s3checksumalgo", dest="s3chksumalgo", help=argparse.SUPPRESS)
     g.add_argument("--s3aclgrantee", default="", metavar="NAME",
                    help="S3 ACL grantee; special canned values private, public-read, "

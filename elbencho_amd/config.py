@@ -247,7 +247,7 @@ class BenchConfig:
     s3_sse_c_key: str = ""         # --s3sseckey (SSE-C base64 key)
     s3_sse_kms_key: str = ""       # --s3ssekmskey (SSE-KMS key id)
     s3_session_token: str = ""     # --s3sessiontoken (x-amz-security-token)
-    s3_chksum_algo: str = ""       # --s3chksumalgo (CRC32|CRC32C|SHA1|SHA256)
+    s3_chksum_algo: str = ""       # --s3chksumalgo (CRC32|CRC32C|CRC64NVME|SHA1|SHA256)
     s3_acl_grantee: str = ""       # --s3aclgrantee (canned ACL or grantee name)
     s3_acl_gtype: str = ""         # --s3aclgtype (id|emailAddress|uri|group)
     s3_acl_put_inline: bool = False  # --s3aclputinl (ACL headers on object PUT)
@@ -380,9 +380,9 @@ class BenchConfig:
                     "upload exceeding the S3 limit of 10,000 parts. "
                     "(--s3nompcheck disables this check.)")
             if self.s3_chksum_algo and self.s3_chksum_algo.upper() not in (
-                    "CRC32", "CRC32C", "SHA1", "SHA256"):
+                    "CRC32", "CRC32C", "CRC64NVME", "SHA1", "SHA256"):
                 raise ConfigError("--s3chksumalgo must be one of "
-                                  "CRC32, CRC32C, SHA1, SHA256")
+                                  "CRC32, CRC32C, CRC64NVME, SHA1, SHA256")
 
         if self.threads < 1:
             raise ConfigError("number of threads must be >= 1")

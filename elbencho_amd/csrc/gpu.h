@@ -85,6 +85,9 @@ double gpuVerifyDiagBenchGBs(uint64_t len, int iters, int dev);
 // off these.
 uint64_t gpuCrcTileBytes();
 uint64_t gpuCrcWaveBytes();
+// The same for the CRC-64/NVME kernel (crc64.h: CRC64_TILE_BYTES, CRC64_WAVE_BYTES).
+uint64_t gpuCrc64TileBytes();
+uint64_t gpuCrc64WaveBytes();
 
 // Diagnostic: the hipGetDeviceCount error string (or "ok: N device(s)").
 std::string gpuProbeError();
@@ -239,6 +242,16 @@ public:
 
     // crcDevAsync + crcFetch of one buffer. Synchronizes.
     uint32_t crcDev(int slot, uint64_t len, CrcAlgo algo);
+
+    // --- CRC-64/NVME of a slot's first len bytes (ebCrc64TilesKernel) ---
+    // The contracts of the 32-bit trio above, with gpuCrc64TileBytes()
+    // tiles: len % 16 == 0 (std::invalid_argument otherwise), len == 0 is a
+    // no-op, contiguous ascending partialBase values between fetches. The
+    // tables and the partials array are this trio's own and allocated on its
+    // first call, so 32-bit and 64-bit calls may interleave on one context.
+    void crc64DevAsync(int slot, uint64_t len, uint64_t partialBase);
+    uint64_t crc64Fetch(uint64_t totalLen, uint64_t tileCount);
+    uint64_t crc64Dev(int slot, uint64_t len);
 
 private:
     struct Impl;

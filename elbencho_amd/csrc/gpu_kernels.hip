@@ -13,12 +13,14 @@
 
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "crc.h"
+#include "crc64.h"
 #include "gpu.h"
 
 namespace eb {
@@ -736,6 +738,106 @@ __global__ __launch_bounds__(256) void ebCrcTilesKernel(const ulonglong2* __rest
     }
 }
 
+// CRC-64/NVME of a device buffer: the contract of ebCrcTilesKernel at 64
+// bits — 16 B/lane reads, one RAW partial per tile written to partial[tile],
+// no atomics, grid-stride over tiles, a short final tile right-aligned in the
+// tile frame, nothing at or past nVec2 read. Geometry and table image come
+// from crc64.h (CRC64_*, crc64BuildTileTables), which also emulates this
+// kernel on the host.
+//
+// At 64 bits a multiply by a constant is eight lookups in 2 KiB tables, and
+// the 32-bit kernel's eight shift operators plus the element tables would
+// fill a CU's 160 KiB of LDS. This kernel keeps only what the inner loop
+// needs, 48 KiB, so three workgroups fit per CU:
+//   - 16 element tables: a lane's 16 B element -> its raw CRC (32 KiB),
+//   - one row-shift operator for the Horner step between rows (16 KiB).
+// There are no lane or wave operators. Raw CRCs are linear, so after its
+// rows each thread multiplies its accumulator once by its own weight,
+// x^(8 * bytes that follow its last-row element in the tile), read from the
+// image into a register at kernel start, with a 64-step shift-and-xor
+// carry-less multiply in registers (gfx950 has none in hardware). The tile's
+// partial is then the plain XOR of the 256 products: wave shuffles, then four
+// words through LDS. That multiply is VALU-only work next to an inner loop
+// of LDS lookups (24 ds_read_b64 per 16 B), so other waves' lookups can
+// overlap it, and CRC64_STEPS_PER_WAVE = 8 rows amortise it
+// (profiles/s3_native_crc64.md).
+__device__ __forceinline__ uint64_t d_crc64Lut8(const uint64_t* tab, uint64_t v)
+{
+    uint64_t r = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) r ^= tab[k * 256 + ((v >> (8 * k)) & 0xFF)];
+    return r;
+}
+
+// a(x) * b(x) mod P, as crc64MulMod
+__device__ __forceinline__ uint64_t d_crc64MulMod(uint64_t a, uint64_t b)
+{
+    uint64_t p = 0;
+#pragma unroll 8
+    for (int i = 63; i >= 0; i--) {
+        p ^= b & (0 - ((a >> i) & 1));
+        b = (b >> 1) ^ (CRC64_NVME_POLY & (0 - (b & 1)));
+    }
+    return p;
+}
+
+__global__ __launch_bounds__(256) void ebCrc64TilesKernel(const ulonglong2* __restrict__ buf,
+                                                          uint64_t nVec2, // # of 16B elements
+                                                          const uint64_t* __restrict__ tables,
+                                                          uint64_t* __restrict__ partial)
+{
+    static_assert(CRC64_WAVES_PER_TILE * CRC64_WAVE_LANES == 256, "one thread per weight");
+    __shared__ __align__(16) uint64_t tab[CRC64_TAB_LDS * 256];
+    __shared__ uint64_t wavePart[CRC64_WAVES_PER_TILE];
+
+    for (int i = threadIdx.x; i < CRC64_TAB_LDS * 256 / 2; i += 256)
+        ((uint4*)tab)[i] = ((const uint4*)tables)[i];
+    const uint64_t weight = tables[CRC64_TAB_WEIGHT * 256 + threadIdx.x];
+    __syncthreads();
+
+    constexpr uint64_t TILE_VEC2 = CRC64_TILE_BYTES / 16;
+    const uint64_t nTiles = (nVec2 + TILE_VEC2 - 1) / TILE_VEC2;
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+
+    for (uint64_t tile = blockIdx.x; tile < nTiles; tile += gridDim.x) {
+        const uint64_t first = tile * TILE_VEC2;
+        const uint64_t have = (nVec2 - first < TILE_VEC2) ? nVec2 - first : TILE_VEC2;
+        const uint64_t pad = TILE_VEC2 - have; // leading zero elements of a short tile
+
+        ulonglong2 v[CRC64_STEPS_PER_WAVE];
+#pragma unroll
+        for (int j = 0; j < CRC64_STEPS_PER_WAVE; j++) { // 16 B/lane coalesced reads
+            uint64_t pos = (uint64_t)(wave * CRC64_STEPS_PER_WAVE + j) * 64 + lane;
+            v[j] = make_ulonglong2(0, 0);
+            if (pos >= pad) v[j] = buf[first + pos - pad];
+        }
+
+        uint64_t acc = 0;
+#pragma unroll
+        for (int j = 0; j < CRC64_STEPS_PER_WAVE; j++)
+            acc = d_crc64Lut8(tab + CRC64_TAB_ROW * 256, acc) ^
+                  d_crc64Lut8(tab + CRC64_TAB_ELEM * 256, v[j].x) ^
+                  d_crc64Lut8(tab + (CRC64_TAB_ELEM + 8) * 256, v[j].y);
+
+        acc = d_crc64MulMod(weight, acc);
+
+        // the weights have placed every value; what is left is an XOR
+#pragma unroll
+        for (int i = 0; i < 6; i++) acc ^= __shfl_down(acc, 1 << i, 64);
+
+        if (lane == 0) wavePart[wave] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t t = 0;
+#pragma unroll
+            for (int w = 0; w < CRC64_WAVES_PER_TILE; w++) t ^= wavePart[w];
+            partial[tile] = t;
+        }
+        __syncthreads(); // wavePart is rewritten in the next pass
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host wrappers
 // ---------------------------------------------------------------------------
@@ -870,6 +972,14 @@ struct GpuCtx::Impl {
     uint64_t crcPartCap = 0;                     // in partials
     struct CrcCall { uint64_t base, len; };
     std::vector<CrcCall> crcPending;             // enqueued since the last fetch
+
+    // CRC-64/NVME state: its own, allocated by the first crc64DevAsync
+    uint64_t* crc64TabDev = nullptr;             // CRC64_TAB_COUNT*256 words
+    std::unique_ptr<Crc64Shift> crc64TileShift;  // host fold: shift by one tile
+    uint64_t* crc64PartDev = nullptr;            // partial[tile], growable
+    uint64_t* crc64PartHost = nullptr;           // pinned mirror
+    uint64_t crc64PartCap = 0;                   // in partials
+    std::vector<CrcCall> crc64Pending;           // enqueued since the last fetch
 };
 
 GpuCtx::GpuCtx(int deviceId, int numSlots, uint64_t bufSize, bool pinnedHostBufs)
@@ -955,6 +1065,9 @@ GpuCtx::~GpuCtx()
         if (p) (void)hipFree(p);
     if (impl->crcPartDev) (void)hipFree(impl->crcPartDev);
     if (impl->crcPartHost) (void)hipHostFree(impl->crcPartHost);
+    if (impl->crc64TabDev) (void)hipFree(impl->crc64TabDev);
+    if (impl->crc64PartDev) (void)hipFree(impl->crc64PartDev);
+    if (impl->crc64PartHost) (void)hipHostFree(impl->crc64PartHost);
     if (impl->stream && impl->ownStream) (void)hipStreamDestroy(impl->stream);
     delete impl;
 }
@@ -1433,6 +1546,95 @@ uint32_t GpuCtx::crcDev(int slot, uint64_t len, CrcAlgo algo)
     impl->crcPending.clear();
     crcDevAsync(slot, len, algo, 0);
     return crcFetch(algo, len, (len + CRC_TILE_BYTES - 1) / CRC_TILE_BYTES);
+}
+
+// --- CRC-64/NVME in HBM: the same trio on state of its own ---
+
+uint64_t gpuCrc64TileBytes() { return CRC64_TILE_BYTES; }
+uint64_t gpuCrc64WaveBytes() { return CRC64_WAVE_BYTES; }
+
+void GpuCtx::crc64DevAsync(int slot, uint64_t len, uint64_t partialBase)
+{
+    requireAligned("crc64DevAsync", len, 16);
+    if (len > impl->slotStride)
+        throw std::invalid_argument("crc64DevAsync: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    if (!len) return;
+    const uint64_t tiles = (len + CRC64_TILE_BYTES - 1) / CRC64_TILE_BYTES;
+
+    if (!impl->crc64TabDev) { // first use: build + upload the table image
+        std::vector<uint64_t> tab = crc64BuildTileTables();
+        HIP_CHECK(hipMalloc(&impl->crc64TabDev, tab.size() * sizeof(uint64_t)));
+        HIP_CHECK(hipMemcpy(impl->crc64TabDev, tab.data(), tab.size() * sizeof(uint64_t),
+                            hipMemcpyHostToDevice));
+        impl->crc64TileShift = std::make_unique<Crc64Shift>(CRC64_TILE_BYTES);
+    }
+
+    if (partialBase + tiles > impl->crc64PartCap) { // grow, keeping earlier partials
+        uint64_t cap = std::max<uint64_t>(4096, impl->crc64PartCap * 2);
+        while (cap < partialBase + tiles) cap *= 2;
+        uint64_t* dev = nullptr;
+        uint64_t* host = nullptr;
+        HIP_CHECK(hipMalloc(&dev, cap * sizeof(uint64_t)));
+        HIP_CHECK(hipHostMalloc(&host, cap * sizeof(uint64_t), hipHostMallocDefault));
+        if (impl->crc64PartDev) {
+            HIP_CHECK(hipStreamSynchronize(impl->stream)); // kernels still writing the old one
+            HIP_CHECK(hipMemcpy(dev, impl->crc64PartDev, impl->crc64PartCap * sizeof(uint64_t),
+                                hipMemcpyDeviceToDevice));
+            (void)hipFree(impl->crc64PartDev);
+            (void)hipHostFree(impl->crc64PartHost);
+        }
+        impl->crc64PartDev = dev;
+        impl->crc64PartHost = host;
+        impl->crc64PartCap = cap;
+    }
+
+    dim3 grid = gridForBytes(tiles * 256); // one workgroup per tile, capped
+    hipLaunchKernelGGL(ebCrc64TilesKernel, grid, dim3(256), 0, impl->stream,
+                       (const ulonglong2*)impl->devBufs[slot], len / 16,
+                       (const uint64_t*)impl->crc64TabDev, impl->crc64PartDev + partialBase);
+    HIP_CHECK(hipGetLastError());
+    impl->crc64Pending.push_back({partialBase, len});
+}
+
+uint64_t GpuCtx::crc64Fetch(uint64_t totalLen, uint64_t tileCount)
+{
+    // the calls since the last fetch must tile [0, tileCount) in order and
+    // add up to totalLen; each call's last tile may be short
+    std::vector<Impl::CrcCall> calls;
+    calls.swap(impl->crc64Pending);
+    uint64_t tiles = 0, bytes = 0;
+    for (const auto& c : calls) {
+        if (c.base != tiles)
+            throw std::invalid_argument("crc64Fetch: partials are not contiguous in call order");
+        tiles += (c.len + CRC64_TILE_BYTES - 1) / CRC64_TILE_BYTES;
+        bytes += c.len;
+    }
+    if (tiles != tileCount || bytes != totalLen)
+        throw std::invalid_argument("crc64Fetch: " + std::to_string(tileCount) + " tiles / " +
+                                    std::to_string(totalLen) + " bytes asked, " +
+                                    std::to_string(tiles) + " / " + std::to_string(bytes) +
+                                    " enqueued");
+    if (!tileCount) return crc64FinishRaw(0, 0);
+
+    HIP_CHECK(hipMemcpyAsync(impl->crc64PartHost, impl->crc64PartDev,
+                             tileCount * sizeof(uint64_t), hipMemcpyDeviceToHost, impl->stream));
+    HIP_CHECK(hipStreamSynchronize(impl->stream));
+
+    const uint64_t* part = impl->crc64PartHost;
+    uint64_t raw = 0;
+    for (const auto& c : calls) {
+        raw = crc64FoldTiles(*impl->crc64TileShift, raw, part, c.len);
+        part += (c.len + CRC64_TILE_BYTES - 1) / CRC64_TILE_BYTES;
+    }
+    return crc64FinishRaw(raw, totalLen);
+}
+
+uint64_t GpuCtx::crc64Dev(int slot, uint64_t len)
+{
+    impl->crc64Pending.clear();
+    crc64DevAsync(slot, len, 0);
+    return crc64Fetch(len, (len + CRC64_TILE_BYTES - 1) / CRC64_TILE_BYTES);
 }
 
 double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev)

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "crc.h"
+#include "crc64.h"
 #include "gpu.h"
 #include "rand.h"
 
@@ -310,19 +311,78 @@ public:
     // crcCombine, with no GPU work.
     uint32_t bodyCrc(uint64_t len, uint64_t patternOff, int64_t salt, CrcAlgo algo)
     {
-        uint32_t crc = 0;
+        return bodyCrcT(Crc32Ops{algo, randCrc[(int)algo]}, len, patternOff, salt);
+    }
+
+    // The same for CRC-64/NVME (x-amz-checksum-crc64nvme), through the same
+    // three branches; the device branch runs ebCrc64TilesKernel.
+    uint64_t bodyCrc64(uint64_t len, uint64_t patternOff, int64_t salt)
+    {
+        return bodyCrcT(Crc64Ops{randCrc64}, len, patternOff, salt);
+    }
+
+    void close() { closeConn(); }
+
+private:
+    template <typename W>
+    struct RandCrcT {
+        bool valid = false;
+        W full = 0; // CRC of randBuf[0, maxBlock)
+        W xp = 0;   // x^(8*maxBlock) mod P
+    };
+    RandCrcT<uint32_t> randCrc[2]; // per CrcAlgo
+    RandCrcT<uint64_t> randCrc64;
+
+    // What bodyCrcT needs of a checksum: the host library and the device trio.
+    struct Crc32Ops {
+        using Word = uint32_t;
+        CrcAlgo algo;
+        RandCrcT<uint32_t>& rand;
+        Word update(Word c, const void* p, size_t n) const { return crcUpdate(algo, c, p, n); }
+        Word shiftPoly(uint64_t n) const { return crcShiftPoly(algo, n); }
+        Word combineXp(Word xp, Word a, Word b) const { return crcCombineXp(algo, xp, a, b); }
+        Word combine(Word a, Word b, uint64_t n) const { return crcCombine(algo, a, b, n); }
+        uint64_t tileBytes() const { return gpuCrcTileBytes(); }
+        void devAsync(GpuCtx& g, int slot, uint64_t n, uint64_t base) const
+        {
+            g.crcDevAsync(slot, n, algo, base);
+        }
+        Word fetch(GpuCtx& g, uint64_t n, uint64_t tiles) const
+        {
+            return g.crcFetch(algo, n, tiles);
+        }
+    };
+    struct Crc64Ops {
+        using Word = uint64_t;
+        RandCrcT<uint64_t>& rand;
+        Word update(Word c, const void* p, size_t n) const { return crc64Update(c, p, n); }
+        Word shiftPoly(uint64_t n) const { return crc64ShiftPoly(n); }
+        Word combineXp(Word xp, Word a, Word b) const { return crc64CombineXp(xp, a, b); }
+        Word combine(Word a, Word b, uint64_t n) const { return crc64Combine(a, b, n); }
+        uint64_t tileBytes() const { return gpuCrc64TileBytes(); }
+        void devAsync(GpuCtx& g, int slot, uint64_t n, uint64_t base) const
+        {
+            g.crc64DevAsync(slot, n, base);
+        }
+        Word fetch(GpuCtx& g, uint64_t n, uint64_t tiles) const { return g.crc64Fetch(n, tiles); }
+    };
+
+    template <typename Ops>
+    typename Ops::Word bodyCrcT(Ops ops, uint64_t len, uint64_t patternOff, int64_t salt)
+    {
+        typename Ops::Word crc = 0;
         uint64_t done = 0;
 
         if (salt < 0) {
-            RandCrc& rc = randCrc[(int)algo];
+            auto& rc = ops.rand;
             if (!rc.valid) {
-                rc.full = crcUpdate(algo, 0, randBuf.data(), maxBlock);
-                rc.xp = crcShiftPoly(algo, maxBlock);
+                rc.full = ops.update(0, randBuf.data(), maxBlock);
+                rc.xp = ops.shiftPoly(maxBlock);
                 rc.valid = true;
             }
             for (; len - done >= maxBlock; done += maxBlock)
-                crc = crcCombineXp(algo, rc.xp, crc, rc.full);
-            return crcUpdate(algo, crc, randBuf.data(), len - done);
+                crc = ops.combineXp(rc.xp, crc, rc.full);
+            return ops.update(crc, randBuf.data(), len - done);
         }
 
         if (gpu && patternOff % 8 == 0) {
@@ -331,10 +391,10 @@ public:
             const uint64_t chunk = std::min<uint64_t>(maxBlock, 2 << 20);
             const int nSlots = gpu->numSlots();
             uint64_t devLen = 0, devTiles = 0; // enqueued, not yet fetched
-            const uint64_t tileBytes = gpuCrcTileBytes();
+            const uint64_t tileBytes = ops.tileBytes();
             auto fetch = [&] {
                 if (!devLen) return;
-                crc = crcCombine(algo, crc, gpu->crcFetch(algo, devLen, devTiles), devLen);
+                crc = ops.combine(crc, ops.fetch(*gpu, devLen, devTiles), devLen);
                 devLen = devTiles = 0;
             };
             int slot = 0;
@@ -343,14 +403,14 @@ public:
                 uint64_t off = patternOff + done;
                 if (n % 16 == 0 && off % 8 == 0) {
                     gpu->fillChecksumDev(slot, n, off, (uint64_t)salt);
-                    gpu->crcDevAsync(slot, n, algo, devTiles);
+                    ops.devAsync(*gpu, slot, n, devTiles);
                     devLen += n;
                     devTiles += (n + tileBytes - 1) / tileBytes;
                     slot = (slot + 1) % nSlots;
                 } else {
                     fetch();
                     fillChecksumCPU(buf, n, off, (uint64_t)salt);
-                    crc = crcUpdate(algo, crc, buf, n);
+                    crc = ops.update(crc, buf, n);
                 }
                 done += n;
             }
@@ -361,21 +421,12 @@ public:
         while (done < len) {
             uint64_t n = std::min<uint64_t>(len - done, maxBlock);
             fillChecksumCPU(buf, n, patternOff + done, (uint64_t)salt);
-            crc = crcUpdate(algo, crc, buf, n);
+            crc = ops.update(crc, buf, n);
             done += n;
         }
         return crc;
     }
 
-    void close() { closeConn(); }
-
-private:
-    struct RandCrc {
-        bool valid = false;
-        uint32_t full = 0; // CRC of randBuf[0, maxBlock)
-        uint32_t xp = 0;   // x^(8*maxBlock) mod P
-    };
-    RandCrc randCrc[2]; // per CrcAlgo
     std::string host;
     int port;
     uint64_t maxBlock;

@@ -15,6 +15,7 @@
 #include <fcntl.h>
 
 #include "crc.h"
+#include "crc64.h"
 #include "engine.h"
 #include "httpdata.h"
 #include "s3srv.h"
@@ -293,18 +294,42 @@ PYBIND11_MODULE(_core, m)
         return crcUpdate(CrcAlgo::CRC32C, 0, buf.data(), buf.size());
     });
 
-    // CRC-32 / CRC-32C host library (csrc/crc.h): algo is "CRC32" or "CRC32C"
-    m.def("crc", [](py::bytes data, const std::string& algo) {
-        CrcAlgo a = crcAlgoFromName(algo);
+    // CRC host libraries (csrc/crc.h, csrc/crc64.h): algo is "CRC32",
+    // "CRC32C" or "CRC64NVME"; the last returns an int of up to 64 bits
+    m.def("crc", [](py::bytes data, const std::string& algo) -> uint64_t {
         std::string buf = data;
+        if (algo == CRC64_NVME_NAME) {
+            py::gil_scoped_release rel;
+            return crc64Update(0, buf.data(), buf.size());
+        }
+        CrcAlgo a = crcAlgoFromName(algo);
         py::gil_scoped_release rel;
         return crcUpdate(a, 0, buf.data(), buf.size());
     }, py::arg("data"), py::arg("algo"));
     // CRC of A||B from the CRCs of A and B (zlib crc32_combine semantics)
-    m.def("crc_combine", [](const std::string& algo, uint32_t crcA, uint32_t crcB,
-                            uint64_t lenB) {
-        return crcCombine(crcAlgoFromName(algo), crcA, crcB, lenB);
+    m.def("crc_combine", [](const std::string& algo, uint64_t crcA, uint64_t crcB,
+                            uint64_t lenB) -> uint64_t {
+        if (algo == CRC64_NVME_NAME) return crc64Combine(crcA, crcB, lenB);
+        CrcAlgo a = crcAlgoFromName(algo);
+        if ((crcA | crcB) >> 32) throw py::type_error(algo + " values are 32 bits wide");
+        return crcCombine(a, (uint32_t)crcA, (uint32_t)crcB, lenB);
     }, py::arg("algo"), py::arg("crc_a"), py::arg("crc_b"), py::arg("len_b"));
+    // Finished CRC from the host emulation of the device tile kernel
+    // (crc64TilesHost + the host fold): the kernel's tables, weights and
+    // geometry checked without a GPU. len(data) % 16 must be 0.
+    m.def("crc_tiles_host", [](py::bytes data, const std::string& algo) -> uint64_t {
+        if (algo != CRC64_NVME_NAME)
+            throw std::invalid_argument("crc_tiles_host: unknown algorithm '" + algo +
+                                        "' (CRC64NVME)");
+        std::string buf = data;
+        if (buf.size() % 16)
+            throw std::invalid_argument("crc_tiles_host: length must be a multiple of 16");
+        py::gil_scoped_release rel;
+        std::vector<uint64_t> part = crc64TilesHost(buf.data(), buf.size());
+        Crc64Shift tileShift(CRC64_TILE_BYTES);
+        return crc64FinishRaw(crc64FoldTiles(tileShift, 0, part.data(), buf.size()),
+                              buf.size());
+    }, py::arg("data"), py::arg("algo") = CRC64_NVME_NAME);
 
     // --- offset generator test hook ---
     m.def("gen_offsets",
@@ -655,8 +680,9 @@ PYBIND11_MODULE(_core, m)
     // Device CRC test helper: data plus `guard` sentinel bytes go into one
     // slot; returns the CRC the tile kernel + host fold give for len(data).
     m.def("gpu_crc", [](py::bytes data, const std::string& algo, int dev, uint64_t guard,
-                        int sentinel) {
-        CrcAlgo a = crcAlgoFromName(algo);
+                        int sentinel) -> uint64_t {
+        const bool is64 = algo == CRC64_NVME_NAME;
+        CrcAlgo a = is64 ? CrcAlgo::CRC32C : crcAlgoFromName(algo);
         std::string buf = data;
         py::gil_scoped_release rel;
         const uint64_t total = buf.size() + guard;
@@ -665,11 +691,40 @@ PYBIND11_MODULE(_core, m)
         std::memset(ctx.hostBuf(0) + buf.size(), sentinel, guard);
         if (total) ctx.copyH2DAsync(0, total);
         ctx.syncStream();
+        if (is64) return ctx.crc64Dev(0, buf.size());
         return ctx.crcDev(0, buf.size(), a);
     }, py::arg("data"), py::arg("algo"), py::arg("dev") = 0, py::arg("guard") = 0,
        py::arg("sentinel") = 0);
-    m.def("gpu_crc_tile_bytes", &gpuCrcTileBytes);
-    m.def("gpu_crc_wave_bytes", &gpuCrcWaveBytes);
+    // One context, CRC32C and CRC64NVME of the same buffer alternating
+    // `rounds` times: [(crc32c, crc64nvme), ...]. The two trios keep separate
+    // state on the context; this shows that neither disturbs the other.
+    m.def("gpu_crc_interleaved", [](py::bytes data, int rounds, int dev) {
+        std::string buf = data;
+        std::vector<std::pair<uint32_t, uint64_t>> out;
+        {
+            py::gil_scoped_release rel;
+            GpuCtx ctx(dev, 1, std::max<uint64_t>(buf.size(), 16), true);
+            std::memcpy(ctx.hostBuf(0), buf.data(), buf.size());
+            if (buf.size()) ctx.copyH2DAsync(0, buf.size());
+            ctx.syncStream();
+            for (int i = 0; i < rounds; i++) {
+                uint32_t c32 = ctx.crcDev(0, buf.size(), CrcAlgo::CRC32C);
+                out.emplace_back(c32, ctx.crc64Dev(0, buf.size()));
+            }
+        }
+        return out;
+    }, py::arg("data"), py::arg("rounds") = 2, py::arg("dev") = 0);
+    // geometry of the device CRC kernel that serves `algo`
+    m.def("gpu_crc_tile_bytes", [](const std::string& algo) {
+        if (algo == CRC64_NVME_NAME) return gpuCrc64TileBytes();
+        (void)crcAlgoFromName(algo);
+        return gpuCrcTileBytes();
+    }, py::arg("algo") = "CRC32C");
+    m.def("gpu_crc_wave_bytes", [](const std::string& algo) {
+        if (algo == CRC64_NVME_NAME) return gpuCrc64WaveBytes();
+        (void)crcAlgoFromName(algo);
+        return gpuCrcWaveBytes();
+    }, py::arg("algo") = "CRC32C");
 
     m.def("gpu_verify_bench",
           [](uint64_t len, int iters, bool lds, int dev) {
@@ -723,8 +778,10 @@ PYBIND11_MODULE(_core, m)
         d["blockvar_gbps"] = timeIt([&] { ctx.blockVarRefillDev(0, len, len / 2, 9); });
         ctx.fillChecksumDev(0, len, 0, 7);
         d["verify_gbps"] = timeIt([&] { (void)ctx.verifyChecksumDev(0, len, 0, 7); });
-        if (len % 16 == 0)
+        if (len % 16 == 0) {
             d["crc32c_gbps"] = timeIt([&] { (void)ctx.crcDev(0, len, CrcAlgo::CRC32C); });
+            d["crc64nvme_gbps"] = timeIt([&] { (void)ctx.crc64Dev(0, len); });
+        }
         d["d2h_gbps"] = timeIt([&] { ctx.copyD2HAsync(0, len); ctx.syncStream(); });
         d["h2d_gbps"] = timeIt([&] { ctx.copyH2DAsync(0, len); ctx.syncStream(); });
         return d;
@@ -822,7 +879,11 @@ PYBIND11_MODULE(_core, m)
              py::arg("pattern_off") = 0, py::arg("salt") = -1)
         .def("body_crc",
              [](HttpDataPlane& h, uint64_t len, uint64_t pattern_off, int64_t salt,
-                const std::string& algo) {
+                const std::string& algo) -> uint64_t {
+                 if (algo == CRC64_NVME_NAME) {
+                     py::gil_scoped_release rel;
+                     return h.bodyCrc64(len, pattern_off, salt);
+                 }
                  CrcAlgo a = crcAlgoFromName(algo);
                  py::gil_scoped_release rel;
                  return h.bodyCrc(len, pattern_off, salt, a);

@@ -33,6 +33,8 @@ from elbencho_amd.histogram import Histogram
 from elbencho_amd.stats import WorkerStats
 
 EMPTY_SHA256 = hashlib.sha256(b"").hexdigest()
+# --s3chksumalgo values whose checksum the native data plane computes itself
+NATIVE_CRC_ALGOS = ("CRC32", "CRC32C", "CRC64NVME")
 
 
 class S3Error(RuntimeError):
@@ -90,11 +92,11 @@ class S3Client:
     def attach_native(self, dev: int, max_block: int) -> bool:
         """Route object-body transfers through the native data plane
         (SigV4 signing stays here). Not used with HTTPS, nor with SHA1 /
-        SHA256 checksums (those need the body bytes in Python). CRC32 and
-        CRC32C stay native: the plane computes the checksum of the body it
-        is about to generate (HttpDataPlane.body_crc — in HBM for pattern
-        bodies when a device is attached)."""
-        if self.secure or self.checksum_algo not in ("", "CRC32", "CRC32C"):
+        SHA256 checksums (those need the body bytes in Python). CRC32,
+        CRC32C and CRC64NVME stay native: the plane computes the checksum of
+        the body it is about to generate (HttpDataPlane.body_crc — in HBM for
+        pattern bodies when a device is attached)."""
+        if self.secure or self.checksum_algo not in ("",) + NATIVE_CRC_ALGOS:
             return False
         self.native = load_core().HttpDataPlane(
             self.host, self.port, dev, max_block,
@@ -118,8 +120,9 @@ class S3Client:
                           query: dict[str, str] | None = None) -> str:
         """PUT with a natively generated body (checksum pattern when
         salt >= 0, random otherwise). Returns the ETag. With a CRC32 /
-        CRC32C checksum_algo the plane computes the body's checksum first
-        and it rides in the signed headers (multipart parts included)."""
+        CRC32C / CRC64NVME checksum_algo the plane computes the body's
+        checksum first and it rides in the signed headers (multipart parts
+        included)."""
         with self.lock:
             headers = dict(self.extra_put_headers)
             if self.checksum_algo:
@@ -129,7 +132,8 @@ class S3Client:
                 crc = self.native.body_crc(length, pattern_off, salt, algo)
                 headers["x-amz-sdk-checksum-algorithm"] = algo
                 headers[f"x-amz-checksum-{algo.lower()}"] = \
-                    base64.b64encode(struct.pack(">I", crc)).decode()
+                    base64.b64encode(struct.pack(
+                        ">Q" if algo == "CRC64NVME" else ">I", crc)).decode()
             req = self._native_raw_request(
                 "PUT", f"/{bucket}/{key}", query, dict(headers), length)
             status, raw_hdrs = self.native.put(req, length, pattern_off, salt)
@@ -271,6 +275,8 @@ class S3Client:
             digest = struct.pack(">I", zlib.crc32(body) & 0xFFFFFFFF)
         elif algo == "CRC32C":
             digest = struct.pack(">I", load_core().crc32c(body))
+        elif algo == "CRC64NVME":
+            digest = struct.pack(">Q", load_core().crc(body, "CRC64NVME"))
         elif algo == "SHA1":
             digest = hashlib.sha1(body).digest()
         else:  # SHA256
@@ -442,8 +448,15 @@ class S3Client:
 
     # --- multipart ---
     def create_multipart(self, bucket: str, key: str) -> str:
+        headers = dict(self.extra_put_headers)
+        if self.checksum_algo == "CRC64NVME":
+            # the only S3 checksum defined over the whole object of a
+            # multipart upload; S3 wants both declared at initiation before
+            # it accepts parts that carry x-amz-checksum-crc64nvme
+            headers["x-amz-checksum-algorithm"] = "CRC64NVME"
+            headers["x-amz-checksum-type"] = "FULL_OBJECT"
         status, data, _ = self.request("POST", f"/{bucket}/{key}", query={"uploads": ""},
-                                       headers=dict(self.extra_put_headers))
+                                       headers=headers)
         self._check(status, data, f"initiate multipart {bucket}/{key}")
         root = ET.fromstring(data)
         ns = root.tag.split("}")[0] + "}" if "}" in root.tag else ""

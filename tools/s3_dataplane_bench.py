@@ -34,8 +34,8 @@ def main() -> int:
     ap.add_argument("--verify", type=int, default=-1)
     ap.add_argument("--iodepth", type=int, default=1)
     ap.add_argument("--chksumalgo", default="",
-                    help="--s3chksumalgo for the run (CRC32/CRC32C keep the "
-                         "native plane; SHA1/SHA256 take the Python path)")
+                    help="--s3chksumalgo for the run (CRC32/CRC32C/CRC64NVME keep "
+                         "the native plane; SHA1/SHA256 take the Python path)")
     args = ap.parse_args()
 
     core = load_core()
