@@ -131,6 +131,21 @@ def build_parser() -> argparse.ArgumentParser:
                         "\"fast\" runs the splitmix-of-index gfx950 kernel "
                         "(6.4 TB/s) and the others the xoshiro256++ kernel. "
                         "(Default: fast)")
+    g.add_argument("--dedupepct", type=int, default=0, metavar="PCT",
+                   help="Write data of which PCT percent of the chunks (--dedupechunk) are "
+                        "duplicates, taken from a pool of 256 chunk contents shared by all "
+                        "threads, files and services; the other chunks are unique. 50 gives "
+                        "a dedupe ratio of about 2:1. 0..100. Not with --verify or "
+                        "--blockvarpct. File, block device and directory paths only. "
+                        "(Default: 0)")
+    g.add_argument("--compresspct", type=int, default=0, metavar="PCT",
+                   help="Write data of which the last PCT percent of every chunk "
+                        "(--dedupechunk) are zeros and the rest random. 50 gives a compress "
+                        "ratio of about 2:1. 0..100. Same restrictions as --dedupepct. "
+                        "(Default: 0)")
+    g.add_argument("--dedupechunk", default="4K", metavar="SIZE",
+                   help="Chunk size of --dedupepct and --compresspct: a power of two in "
+                        "512..16M; the block size should be a multiple of it. (Default: 4K)")
 
     g = p.add_argument_group("GPU (MI355X)")
     g.add_argument("--gpuids", default="", metavar="IDS",
@@ -505,6 +520,9 @@ def args_to_config(args: argparse.Namespace) -> BenchConfig:
     cfg.flock_mode = args.flock
     cfg.blockvar_pct = args.blockvarpct
     cfg.blockvar_algo = args.blockvaralgo
+    cfg.dedupe_pct = args.dedupepct
+    cfg.compress_pct = args.compresspct
+    cfg.dedupe_chunk = parse_size(args.dedupechunk)
 
     cfg.gpu_ids = parse_gpu_ids(args.gpuids)
     cfg.gpu_per_service = args.gpuperservice

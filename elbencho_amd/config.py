@@ -115,6 +115,9 @@ class BenchConfig:
     flock_mode: str = ""           # --flock ("range"|"full")
     blockvar_pct: int = 100        # --blockvarpct
     blockvar_algo: str = "fast"    # --blockvaralgo
+    dedupe_pct: int = 0            # --dedupepct (percent of chunks from the shared pool)
+    compress_pct: int = 0          # --compresspct (percent of each chunk that is zero)
+    dedupe_chunk: int = 4096       # --dedupechunk (chunk size of the two above)
 
     # --- GPU ---
     gpu_ids: list[int] = field(default_factory=list)  # --gpuids
@@ -428,6 +431,23 @@ class BenchConfig:
             if self.bench_mode in ("s3", "hdfs", "netbench"):
                 raise ConfigError("--verifydiag supports file, block device and "
                                   "directory paths only")
+        if not (0 <= self.dedupe_pct <= 100):
+            raise ConfigError("dedupepct must be in 0..100")
+        if not (0 <= self.compress_pct <= 100):
+            raise ConfigError("compresspct must be in 0..100")
+        if self.dedupe_pct or self.compress_pct:
+            c = self.dedupe_chunk
+            if not (512 <= c <= 16 << 20) or c & (c - 1):
+                raise ConfigError("--dedupechunk must be a power of two in 512..16M")
+            if self.verify >= 0:
+                raise ConfigError("--dedupepct/--compresspct cannot be used together with "
+                                  "--verify")
+            if self.blockvar_pct != 100:
+                raise ConfigError("--dedupepct/--compresspct cannot be used together with "
+                                  "--blockvarpct")
+            if self.bench_mode in ("s3", "hdfs", "netbench"):
+                raise ConfigError("--dedupepct/--compresspct supports file, block device "
+                                  "and directory paths only")
         # reference ProgArgs.cpp:1548-1556: readback verification and inline
         # reads are sync-engine features
         if self.verify_direct and (self.verify < 0 or not self.run_write):
@@ -538,6 +558,9 @@ class BenchConfig:
             verify_direct=self.verify_direct,
             blockvar_pct=self.blockvar_pct,
             blockvar_algo=self.blockvar_algo,
+            dedupe_pct=self.dedupe_pct,
+            compress_pct=self.compress_pct,
+            dedupe_chunk=self.dedupe_chunk,
             rand_algo=self.rand_algo,
             gpu_ids=self.gpu_ids,
             gpu_pinned=self.gpu_pinned,

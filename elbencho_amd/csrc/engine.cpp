@@ -119,6 +119,37 @@ static inline uint64_t mixValueAt(uint64_t alignedOff, uint64_t salt, uint64_t r
     return (rel < mixLen) ? splitmix64Of(x) : x;
 }
 
+// --dedupepct / --compresspct pattern (CPU side; stated at engine.h)
+void fillReduceCPU(char* buf, uint64_t len, uint64_t firstChunk, uint64_t chunkBytes,
+                   uint64_t randBytes, int dedupePct, uint64_t pool, uint64_t uniqSeed,
+                   uint64_t poolSeed)
+{
+    constexpr uint64_t GOLD = 0x9E3779B97F4A7C15ULL;
+    const uint64_t d = (uint64_t)dedupePct;
+    uint64_t n = firstChunk;
+    for (uint64_t pos = 0; pos < len; pos += chunkBytes, n++) {
+        const uint64_t chunkLen = std::min(chunkBytes, len - pos);
+        const uint64_t randLen = std::min(randBytes, chunkLen);
+        const bool dup = ((n + 1) * d) / 100 > (n * d) / 100;
+        const uint64_t key = dup ? splitmix64Of(poolSeed + (splitmix64Of(uniqSeed ^ n) % pool))
+                                 : splitmix64Of(uniqSeed ^ splitmix64Of(n));
+        for (uint64_t o = 0; o < randLen; o += 8) {
+            const uint64_t v = splitmix64Of(key + (o / 8) * GOLD);
+            std::memcpy(buf + pos + o, &v, std::min<uint64_t>(8, randLen - o));
+        }
+        std::memset(buf + pos + randLen, 0, chunkLen - randLen);
+    }
+}
+
+ReduceSeeds reduceSeeds(uint64_t benchSeed, int phaseSeq, int globalRank)
+{
+    const uint64_t phaseSeed = benchSeed + 0x9E3779B97F4A7C15ULL * (uint64_t)phaseSeq;
+    ReduceSeeds s;
+    s.uniq = splitmix64Of(phaseSeed ^ (0xD1B54A32D192ED03ULL * (uint64_t)(globalRank + 1)));
+    s.pool = splitmix64Of(benchSeed ^ 0x5DED0C0DE5EED001ULL);
+    return s;
+}
+
 void fillChecksumMixCPU(char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
                         uint64_t blockSize, uint64_t mixLen)
 {
@@ -764,6 +795,26 @@ void Worker::preWriteFill(int slot, uint64_t len, uint64_t fileOff)
         else
             fillChecksumCPU(buf, len, fileOff, (uint64_t)cfg.verifySalt);
         if (gpu) { // keep device buffer coherent for the D2H staging copy
+            gpu->copyH2DAsync(slot, len);
+            gpu->syncStream();
+        }
+        return;
+    }
+
+    if (eng.reduce) {
+        // --dedupepct / --compresspct: the next ceil(len / chunk) chunks of
+        // this worker's sequence, whatever the file offset
+        const uint64_t first = reduceNextChunk;
+        reduceNextChunk += (len + cfg.dedupeChunk - 1) / cfg.dedupeChunk;
+        if (gpu && (len % 16 == 0)) {
+            gpu->fillReduceDev(slot, len, first, cfg.dedupeChunk, eng.reduceRandBytes,
+                               cfg.dedupePct, REDUCE_POOL_CHUNKS, reduceSeed.uniq,
+                               reduceSeed.pool);
+            return;
+        }
+        fillReduceCPU(buf, len, first, cfg.dedupeChunk, eng.reduceRandBytes, cfg.dedupePct,
+                      REDUCE_POOL_CHUNKS, reduceSeed.uniq, reduceSeed.pool);
+        if (gpu) {
             gpu->copyH2DAsync(slot, len);
             gpu->syncStream();
         }
@@ -2961,6 +3012,7 @@ void Worker::threadMain()
                                    phaseSeed ^ (0xBF58476D1CE4E5B9ULL * (globalRank + 1))));
             fillRng.reset(makeRandAlgo(cfg.blockVarAlgo,
                                        phaseSeed ^ (0x94D049BB133111EBULL * (globalRank + 1))));
+            reduceSeed = reduceSeeds(cfg.benchSeed, eng.phaseSeq, globalRank);
 
             // --rwmixthr: first N threads of a write phase only read
             isDedicatedReader =
@@ -2982,6 +3034,7 @@ void Worker::threadMain()
                                      eng.currentPhase == Phase::READ ||
                                      eng.currentPhase == Phase::STAT);
             do {
+                reduceNextChunk = 0;
                 runPhase();
             } while (loopingPhase && !eng.interruptFlag.load(std::memory_order_relaxed));
         } catch (const InterruptedError&) {
@@ -3016,6 +3069,22 @@ Engine::Engine(EngineConfig cfgIn) : cfg(std::move(cfgIn))
         // overflow only for block sizes beyond 2^57
         verifyMixLen = (uint64_t)((unsigned __int128)cfg.blockSize * cfg.verifyMixPct / 100)
                        & ~7ULL;
+    }
+
+    if (cfg.dedupePct < 0 || cfg.dedupePct > 100)
+        throw std::invalid_argument("dedupe_pct must be in 0..100");
+    if (cfg.compressPct < 0 || cfg.compressPct > 100)
+        throw std::invalid_argument("compress_pct must be in 0..100");
+    if (cfg.dedupePct > 0 || cfg.compressPct > 0) {
+        if (cfg.verifySalt >= 0)
+            throw std::invalid_argument(
+                "dedupe_pct / compress_pct cannot be used together with verify_salt");
+        if (cfg.dedupeChunk < 16 || (cfg.dedupeChunk & (cfg.dedupeChunk - 1)) ||
+            cfg.dedupeChunk > (1ULL << 40))
+            throw std::invalid_argument(
+                "dedupe_chunk must be a power of two in 16..2^40");
+        reduce = true;
+        reduceRandBytes = (cfg.dedupeChunk * (uint64_t)(100 - cfg.compressPct) / 100) & ~15ULL;
     }
 }
 

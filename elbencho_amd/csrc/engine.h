@@ -64,6 +64,11 @@ struct EngineConfig {
     bool readInline = false;  // read each file back right after writing it
     bool statInline = false;  // fstat right after open in dir mode
     int blockVarPct = 100;
+    // --dedupepct / --compresspct: write payloads with set reduction ratios
+    // (on iff either percentage is > 0; see fillReduceCPU)
+    int dedupePct = 0;
+    int compressPct = 0;
+    uint64_t dedupeChunk = 4096;
     std::string blockVarAlgo = "fast";
     std::string randAlgo = "fast";
 
@@ -122,6 +127,12 @@ struct EngineConfig {
     bool dynamicSlice = false;
 
     uint64_t benchSeed = 0x243F6A8885A308D3ULL; // per-run; Python sets per iteration
+};
+
+// --dedupepct / --compresspct seeds: uniq differs per worker and phase, pool
+// depends on the run's seed alone (shared by all workers, files and services)
+struct ReduceSeeds {
+    uint64_t uniq = 0, pool = 0;
 };
 
 struct WorkerResult {
@@ -267,6 +278,10 @@ private:
     std::unique_ptr<GpuCtx> gpu;
     std::unique_ptr<RandAlgo> rng;        // offsets
     std::unique_ptr<RandAlgo> fillRng;    // block variance fill
+    // --dedupepct / --compresspct: number of the next chunk this worker
+    // generates (0 at the start of a phase and of every --infloop pass)
+    uint64_t reduceNextChunk = 0;
+    ReduceSeeds reduceSeed;
     RateLimiter rateLimiter;
 };
 
@@ -357,6 +372,12 @@ public:
     bool verifyMix = false;
     uint64_t verifyMixLen = 0;
 
+    // --dedupepct / --compresspct, fixed at construction: on iff either
+    // percentage is > 0; the first reduceRandBytes bytes of every chunk are
+    // random, the rest zero
+    bool reduce = false;
+    uint64_t reduceRandBytes = 0;
+
     // GPU contexts cached across phases (hipMalloc + pinned allocs are
     // expensive; reusing them keeps phase setup off the measured path)
     std::mutex gpuCacheMtx;
@@ -404,6 +425,23 @@ void fillChecksumMixCPU(char* buf, uint64_t len, uint64_t fileOff, uint64_t salt
 uint64_t verifyChecksumMixCPU(const char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
                               uint64_t blockSize, uint64_t mixLen);
 
+// --dedupepct / --compresspct pattern. A worker numbers the chunks (chunkBytes
+// each, a power of two >= 16) it generates in a phase n = 0, 1, 2, ...; with
+// mix = splitmix64 of a value and GOLD = 0x9E3779B97F4A7C15, all mod 2^64:
+//   dup(n) = ((n+1) * dedupePct) / 100 > (n * dedupePct) / 100
+//   key(n) = dup(n) ? mix(poolSeed + (mix(uniqSeed ^ n) % pool))
+//                   : mix(uniqSeed ^ mix(n))
+//   8-byte word i of chunk n = (8*i < randBytes) ? mix(key(n) + i * GOLD) : 0
+// Pool chunks (one of `pool` contents, the same for every worker of a run)
+// deduplicate; the zero tail compresses. fillReduceCPU writes chunks
+// firstChunk, firstChunk+1, ... into buf and cuts the last one at len (any
+// len); randBytes is a multiple of 16 and <= chunkBytes, pool >= 1.
+constexpr uint64_t REDUCE_POOL_CHUNKS = 256;
+void fillReduceCPU(char* buf, uint64_t len, uint64_t firstChunk, uint64_t chunkBytes,
+                   uint64_t randBytes, int dedupePct, uint64_t pool, uint64_t uniqSeed,
+                   uint64_t poolSeed);
+// the seeds a worker uses in the phase with sequence number phaseSeq
+ReduceSeeds reduceSeeds(uint64_t benchSeed, int phaseSeq, int globalRank);
 
 // --verifydiag on a host buffer: the contract of GpuVerifyDiag (gpu.h), added
 // into `acc` (a default-constructed record is empty). Any alignment; a word

@@ -222,6 +222,17 @@ public:
     void blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint64_t seed,
                            bool fastAlgo = false);
 
+    // --dedupepct / --compresspct fill (ebFillReduceKernel): the slot's first
+    // len bytes become chunks firstChunk, firstChunk+1, ... of the pattern
+    // that fillReduceCPU (engine.h) states, the last one cut at len. Requires
+    // len % 16 == 0; chunkBytes a power of two >= 16; randBytes a multiple of
+    // 16 and <= chunkBytes; dedupePct in 0..100; pool >= 1; firstChunk < 2^56;
+    // else std::invalid_argument. A pure function of its arguments: it does
+    // not advance the fill counter that fillRandDev and blockVarRefillDev use.
+    void fillReduceDev(int slot, uint64_t len, uint64_t firstChunk, uint64_t chunkBytes,
+                       uint64_t randBytes, int dedupePct, uint64_t pool, uint64_t uniqSeed,
+                       uint64_t poolSeed);
+
     // --- CRC-32 / CRC-32C of a slot's first len bytes, computed in HBM ---
     // Everything these need (byte tables, the partials array) is allocated
     // on the first call, so runs without a checksum pay nothing.

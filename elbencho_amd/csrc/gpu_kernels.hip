@@ -170,6 +170,80 @@ __global__ __launch_bounds__(256) void ebBlockVarFastKernel(ulonglong2* __restri
     }
 }
 
+// --dedupepct / --compresspct pattern (docs/usage.md, "Data reduction"): the
+// buffer is a run of chunks numbered firstChunk, firstChunk+1, ...; chunk n
+// holds randVec2 16 B elements of splitmix64(key(n) + word * GOLD) and zeros
+// after them. key(n) is a pool key (one of `pool` contents that depend on
+// poolSeed alone) for dedupePct of 100 chunks, else unique to (uniqSeed, n).
+__device__ __forceinline__ uint64_t d_mix64(uint64_t x)
+{
+    return d_splitmix64(x);
+}
+
+// n = firstChunk + j is a pool chunk iff floor((n+1)*d/100) > floor(n*d/100),
+// i.e. iff (n*d) % 100 + d >= 100. Only n % 100 matters, so the host passes
+// firstMod = firstChunk % 100 and the 64-bit product never forms.
+__device__ __forceinline__ uint64_t d_reduceKey(uint64_t firstChunk, uint32_t firstMod,
+                                                uint64_t j, uint32_t dedupePct, uint64_t pool,
+                                                uint64_t uniqSeed, uint64_t poolSeed)
+{
+    const uint64_t n = firstChunk + j;
+    const uint32_t nMod = (firstMod + (uint32_t)(j % 100)) % 100;
+    if ((nMod * dedupePct) % 100 + dedupePct >= 100) {
+        const uint64_t h = d_mix64(uniqSeed ^ n);
+        // the engine's pool size is a power of two: no 64-bit division then
+        const uint64_t member = (pool & (pool - 1)) ? h % pool : h & (pool - 1);
+        return d_mix64(poolSeed + member);
+    }
+    return d_mix64(uniqSeed ^ d_mix64(n));
+}
+
+// Pins a workgroup-uniform value to scalar registers. Without it the compiler
+// merges the last hash of the uniform key with the per-lane one of the small-
+// chunk path and runs it once per element on the vector unit.
+__device__ __forceinline__ uint64_t d_uniform64(uint64_t v)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// One workgroup step writes 256 consecutive 16 B elements = 4 KiB. With
+// chunks of 4 KiB and more (vecShift >= 8) those lie in one chunk, so the
+// chunk number and its key depend on the step alone: they are uniform over
+// the workgroup and cost one computation per chunk and wave, not per element.
+// Smaller chunks compute the key per lane. Lanes in the zero tail of a chunk
+// skip the hashing. No LDS, no atomics.
+__global__ __launch_bounds__(256) void ebFillReduceKernel(
+    ulonglong2* __restrict__ buf, uint64_t nVec2, uint64_t firstChunk, uint32_t firstMod,
+    uint32_t vecShift,  // log2(16 B elements per chunk)
+    uint64_t randVec2,  // random 16 B elements per chunk, <= 1 << vecShift
+    uint32_t dedupePct, uint64_t pool, uint64_t uniqSeed, uint64_t poolSeed)
+{
+    const uint64_t nSteps = (nVec2 + 255) / 256;
+    const uint64_t vecMask = (1ULL << vecShift) - 1;
+    for (uint64_t step = blockIdx.x; step < nSteps; step += gridDim.x) {
+        const uint64_t idx = step * 256 + threadIdx.x;
+        const uint64_t pos = idx & vecMask; // element within its chunk
+        ulonglong2 val;
+        val.x = 0;
+        val.y = 0;
+        if (pos < randVec2) {
+            uint64_t key; // two calls: the first one's arguments are all uniform
+            if (vecShift >= 8)
+                key = d_uniform64(d_reduceKey(firstChunk, firstMod, step >> (vecShift - 8),
+                                              dedupePct, pool, uniqSeed, poolSeed));
+            else
+                key = d_reduceKey(firstChunk, firstMod, idx >> vecShift, dedupePct, pool,
+                                  uniqSeed, poolSeed);
+            const uint64_t s0 = key + pos * 2 * 0x9E3779B97F4A7C15ULL;
+            val.x = d_mix64(s0);
+            val.y = d_mix64(s0 + 0x9E3779B97F4A7C15ULL);
+        }
+        if (idx < nVec2) buf[idx] = val;
+    }
+}
+
 // Integrity fill: u64 at file offset (fileOff + i*8) = fileOff + i*8 + salt.
 // 16 B/lane vectorized main loop (same idiom as the other fill kernels);
 // an odd final u64 is handled by the first thread.
@@ -1453,6 +1527,49 @@ void GpuCtx::blockVarRefillDev(int slot, uint64_t len, uint64_t refillLen, uint6
                            (ulonglong2*)impl->devBufs[slot], nVec2, refillVec2,
                            seed + seq * 0x9E3779B9ULL, fillConst);
     }
+    HIP_CHECK(hipGetLastError());
+}
+
+// --dedupepct / --compresspct launch contract on top of requireAligned(len 16)
+static void requireReduceGeometry(const char* what, uint64_t firstChunk, uint64_t chunkBytes,
+                                  uint64_t randBytes, int dedupePct, uint64_t pool)
+{
+    if (chunkBytes < 16 || (chunkBytes & (chunkBytes - 1)))
+        throw std::invalid_argument(std::string(what) + ": chunk size " +
+                                    std::to_string(chunkBytes) +
+                                    " is not a power of two >= 16");
+    if (randBytes % 16 || randBytes > chunkBytes)
+        throw std::invalid_argument(std::string(what) + ": random length " +
+                                    std::to_string(randBytes) +
+                                    " is not a multiple of 16 within the chunk size " +
+                                    std::to_string(chunkBytes));
+    if (dedupePct < 0 || dedupePct > 100)
+        throw std::invalid_argument(std::string(what) + ": dedupe percentage " +
+                                    std::to_string(dedupePct) + " is not in 0..100");
+    if (!pool)
+        throw std::invalid_argument(std::string(what) + ": pool size must be >= 1");
+    // the kernel decides pool chunks from n % 100; that equals the pattern's
+    // (n+1)*d/100 > n*d/100 as long as the 64-bit products do not wrap
+    if (firstChunk >= (1ULL << 56))
+        throw std::invalid_argument(std::string(what) + ": first chunk " +
+                                    std::to_string(firstChunk) + " is not below 2^56");
+}
+
+void GpuCtx::fillReduceDev(int slot, uint64_t len, uint64_t firstChunk, uint64_t chunkBytes,
+                           uint64_t randBytes, int dedupePct, uint64_t pool,
+                           uint64_t uniqSeed, uint64_t poolSeed)
+{
+    requireAligned("fillReduceDev", len, 16);
+    requireReduceGeometry("fillReduceDev", firstChunk, chunkBytes, randBytes, dedupePct, pool);
+    if (len > impl->slotStride)
+        throw std::invalid_argument("fillReduceDev: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    uint64_t nVec2 = len / 16;
+    if (!nVec2) return;
+    hipLaunchKernelGGL(ebFillReduceKernel, gridForBytes(nVec2), dim3(256), 0, impl->stream,
+                       (ulonglong2*)impl->devBufs[slot], nVec2, firstChunk,
+                       (uint32_t)(firstChunk % 100), (uint32_t)__builtin_ctzll(chunkBytes / 16),
+                       randBytes / 16, (uint32_t)dedupePct, pool, uniqSeed, poolSeed);
     HIP_CHECK(hipGetLastError());
 }
 

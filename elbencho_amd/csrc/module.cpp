@@ -37,6 +37,19 @@ void requireMixArgs(const char* what, uint64_t blockSize, uint64_t mixLen)
                                     "mix_len a multiple of 8 not above it");
 }
 
+// geometry fillReduceCPU takes for granted (the engine checks it once, in its
+// constructor; GpuCtx::fillReduceDev checks it per call)
+void requireReduceArgs(const char* what, uint64_t chunk, uint64_t randBytes, int dedupePct,
+                       uint64_t pool)
+{
+    if (chunk < 16 || (chunk & (chunk - 1)) || randBytes % 16 || randBytes > chunk ||
+        dedupePct < 0 || dedupePct > 100 || !pool)
+        throw std::invalid_argument(std::string(what) +
+                                    ": chunk must be a power of two >= 16, rand_bytes a "
+                                    "multiple of 16 not above it, dedupe_pct in 0..100 and "
+                                    "pool >= 1");
+}
+
 // a GpuVerifyDiag as a dict keyed by the record's field names
 py::dict diagToDict(const GpuVerifyDiag& r)
 {
@@ -132,6 +145,9 @@ EngineConfig configFromDict(const py::dict& d)
         c.netDevs = d["netdevs"].cast<std::vector<std::string>>();
     c.blockVarPct = (int)getI("blockvar_pct", 100);
     c.blockVarAlgo = getS("blockvar_algo", "fast");
+    c.dedupePct = (int)getI("dedupe_pct", 0);
+    c.compressPct = (int)getI("compress_pct", 0);
+    c.dedupeChunk = getU64("dedupe_chunk", 4096);
     c.randAlgo = getS("rand_algo", "balanced_single");
     if (d.contains("gpu_ids")) c.gpuIDs = d["gpu_ids"].cast<std::vector<int>>();
     c.gpuPinnedHostBufs = getB("gpu_pinned", true);
@@ -256,6 +272,24 @@ PYBIND11_MODULE(_core, m)
         return verifyChecksumMixCPU(buf.data(), buf.size(), fileOff, salt, blockSize, mixLen);
     }, py::arg("data"), py::arg("file_off"), py::arg("salt"), py::arg("block_size"),
        py::arg("mix_len"));
+
+    // --dedupepct / --compresspct pattern on the CPU (tests tie it to the
+    // numpy model) and the seeds the engine derives for a worker and phase
+    m.def("fill_reduce", [](uint64_t len, uint64_t firstChunk, uint64_t chunk,
+                            uint64_t randBytes, int dedupePct, uint64_t pool,
+                            uint64_t uniqSeed, uint64_t poolSeed) {
+        requireReduceArgs("fill_reduce", chunk, randBytes, dedupePct, pool);
+        std::string buf(len, '\xA5');
+        fillReduceCPU(buf.data(), len, firstChunk, chunk, randBytes, dedupePct, pool, uniqSeed,
+                      poolSeed);
+        return py::bytes(buf);
+    }, py::arg("len"), py::arg("first_chunk"), py::arg("chunk"), py::arg("rand_bytes"),
+       py::arg("dedupe_pct"), py::arg("pool"), py::arg("uniq_seed"), py::arg("pool_seed"));
+    m.def("reduce_seeds", [](uint64_t benchSeed, int phaseSeq, int rank) {
+        ReduceSeeds s = reduceSeeds(benchSeed, phaseSeq, rank);
+        return py::make_tuple(s.uniq, s.pool);
+    }, py::arg("bench_seed"), py::arg("phase_seq"), py::arg("rank"));
+    m.attr("REDUCE_POOL_CHUNKS") = REDUCE_POOL_CHUNKS;
 
     // --verifydiag on the CPU; block_size 0 selects the plain pattern
     m.def("verify_diag", [](py::bytes data, uint64_t fileOff, uint64_t salt,
@@ -755,6 +789,32 @@ PYBIND11_MODULE(_core, m)
     }, py::arg("len"), py::arg("refill_len"), py::arg("seed"), py::arg("dev") = 0,
        py::arg("fast") = false);
 
+    // Guarded --dedupepct / --compresspct fill: len+pad device bytes preset to
+    // `sentinel`, one fillReduceDev of len bytes, all len+pad bytes returned.
+    // then_blockvar_seed: a fast block-variance refill of the same len bytes
+    // (half random) follows on the same context and is what comes back; it is
+    // that context's fill call 1 iff fillReduceDev took no fill-call number.
+    m.def("gpu_fill_reduce", [](uint64_t len, uint64_t firstChunk, uint64_t chunk,
+                                uint64_t randBytes, int dedupePct, uint64_t pool,
+                                uint64_t uniqSeed, uint64_t poolSeed, int dev, uint64_t pad,
+                                int sentinel, std::optional<uint64_t> thenBlockVarSeed) {
+        const uint64_t total = len + pad;
+        GpuCtx ctx(dev, 1, std::max<uint64_t>(total, 16), true);
+        std::memset(ctx.hostBuf(0), sentinel, total);
+        if (total) ctx.copyH2DAsync(0, total);
+        ctx.syncStream();
+        ctx.fillReduceDev(0, len, firstChunk, chunk, randBytes, dedupePct, pool, uniqSeed,
+                          poolSeed);
+        if (thenBlockVarSeed) ctx.blockVarRefillDev(0, len, len / 2, *thenBlockVarSeed, true);
+        std::memset(ctx.hostBuf(0), ~sentinel, total); // D2H must overwrite all of it
+        if (total) ctx.copyD2HAsync(0, total);
+        ctx.syncStream();
+        return py::bytes(ctx.hostBuf(0), total);
+    }, py::arg("len"), py::arg("first_chunk"), py::arg("chunk"), py::arg("rand_bytes"),
+       py::arg("dedupe_pct"), py::arg("pool"), py::arg("uniq_seed"), py::arg("pool_seed"),
+       py::arg("dev") = 0, py::arg("pad") = 0, py::arg("sentinel") = 0xA5,
+       py::arg("then_blockvar_seed") = py::none());
+
     // Kernel micro-benchmark: bandwidth of the gfx950 fill/verify kernels and
     // the staging copies on one device buffer (GB/s, stream-synchronized).
     m.def("gpu_kernel_bench", [](uint64_t len, int iters, int dev) {
@@ -774,6 +834,13 @@ PYBIND11_MODULE(_core, m)
         d["fill_fast_gbps"] = timeIt([&] { ctx.fillRandDev(0, len, 42, true); });
         d["blockvar_fast_gbps"] =
             timeIt([&] { ctx.blockVarRefillDev(0, len, len / 2, 9, true); });
+        if (len % 16 == 0) { // --dedupepct 50 --compresspct 50 at the default chunk size
+            uint64_t chunks = 0;
+            d["fill_reduce_gbps"] = timeIt([&] {
+                ctx.fillReduceDev(0, len, chunks, 4096, 2048, 50, REDUCE_POOL_CHUNKS, 42, 43);
+                chunks += (len + 4095) / 4096;
+            });
+        }
         d["fill_checksum_gbps"] = timeIt([&] { ctx.fillChecksumDev(0, len, 0, 7); });
         d["blockvar_gbps"] = timeIt([&] { ctx.blockVarRefillDev(0, len, len / 2, 9); });
         ctx.fillChecksumDev(0, len, 0, 7);
@@ -966,6 +1033,9 @@ PYBIND11_MODULE(_core, m)
                                        py::bytes(snap.bytes.data(), snap.bytes.size()));
              },
              py::arg("local_rank") = 0)
+        // sequence number of the current (or last) phase: 0 before the first
+        // start_phase, +1 per start_phase; the per-phase seeds derive from it
+        .def_property_readonly("phase_seq", [](Engine& e) { return e.phaseSeq; })
         .def("planned_work", [](Engine& e, int phaseCode) {
             auto pw = e.plannedWork((Phase)phaseCode);
             return py::make_tuple(pw.first, pw.second);
