@@ -146,6 +146,14 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--dedupechunk", default="4K", metavar="SIZE",
                    help="Chunk size of --dedupepct and --compresspct: a power of two in "
                         "512..16M; the block size should be a multiple of it. (Default: 4K)")
+    g.add_argument("--dedupeverify", type=int, default=-1, metavar="SALT",
+                   help="With --dedupepct and/or --compresspct: make the data a function of "
+                        "SALT (>= 0), the file and the file offset instead of thread and "
+                        "phase, and check every block on read (in HBM with --gpuids). Files "
+                        "still share the pool of duplicate chunks, unique chunks differ "
+                        "between files. The block size must be a multiple of --dedupechunk. "
+                        "Not with --verify, --verifymixpct, --verifydiag or unaligned random "
+                        "offsets. (Default: unset)")
 
     g = p.add_argument_group("GPU (MI355X)")
     g.add_argument("--gpuids", default="", metavar="IDS",
@@ -523,6 +531,7 @@ def args_to_config(args: argparse.Namespace) -> BenchConfig:
     cfg.dedupe_pct = args.dedupepct
     cfg.compress_pct = args.compresspct
     cfg.dedupe_chunk = parse_size(args.dedupechunk)
+    cfg.dedupe_verify = args.dedupeverify
 
     cfg.gpu_ids = parse_gpu_ids(args.gpuids)
     cfg.gpu_per_service = args.gpuperservice

@@ -118,6 +118,7 @@ class BenchConfig:
     dedupe_pct: int = 0            # --dedupepct (percent of chunks from the shared pool)
     compress_pct: int = 0          # --compresspct (percent of each chunk that is zero)
     dedupe_chunk: int = 4096       # --dedupechunk (chunk size of the two above)
+    dedupe_verify: int = -1        # --dedupeverify SALT (position-keyed, checked on read)
 
     # --- GPU ---
     gpu_ids: list[int] = field(default_factory=list)  # --gpuids
@@ -414,6 +415,26 @@ class BenchConfig:
                                   "file/bdev mode (--nodiocheck to skip this check)")
         if self.verify >= 0 and self.random and not self.rand_aligned:
             raise ConfigError("--verify cannot be used with unaligned random offsets")
+        if self.dedupe_verify < -1:
+            raise ConfigError("--dedupeverify needs a salt >= 0")
+        if self.dedupe_verify >= 0:
+            if not (self.dedupe_pct or self.compress_pct):
+                raise ConfigError("--dedupeverify requires a non-zero --dedupepct or "
+                                  "--compresspct")
+            for other, on in (("--verify", self.verify >= 0),
+                              ("--verifymixpct", self.verify_mix_pct != -1),
+                              ("--verifydiag", self.verify_diag)):
+                if on:
+                    raise ConfigError("--dedupeverify cannot be used together with " + other)
+            if self.random and not self.rand_aligned:
+                raise ConfigError("--dedupeverify cannot be used with unaligned random "
+                                  "offsets")
+            if self.bench_mode in ("s3", "hdfs", "netbench"):
+                raise ConfigError("--dedupeverify supports file, block device and "
+                                  "directory paths only")
+            if (self.run_write or self.run_read) and self.block_size % self.dedupe_chunk:
+                raise ConfigError("--dedupeverify requires a block size that is a multiple "
+                                  "of --dedupechunk")
         if self.verify_mix_pct != -1:
             if not (0 <= self.verify_mix_pct <= 100):
                 raise ConfigError("verifymixpct must be in 0..100")
@@ -561,6 +582,7 @@ class BenchConfig:
             dedupe_pct=self.dedupe_pct,
             compress_pct=self.compress_pct,
             dedupe_chunk=self.dedupe_chunk,
+            reduce_verify_salt=self.dedupe_verify,
             rand_algo=self.rand_algo,
             gpu_ids=self.gpu_ids,
             gpu_pinned=self.gpu_pinned,

@@ -120,6 +120,14 @@ static inline uint64_t mixValueAt(uint64_t alignedOff, uint64_t salt, uint64_t r
 }
 
 // --dedupepct / --compresspct pattern (CPU side; stated at engine.h)
+static inline uint64_t reduceKeyCPU(uint64_t n, uint64_t d, uint64_t pool, uint64_t uniqSeed,
+                                    uint64_t poolSeed)
+{
+    const bool dup = ((n + 1) * d) / 100 > (n * d) / 100;
+    return dup ? splitmix64Of(poolSeed + (splitmix64Of(uniqSeed ^ n) % pool))
+               : splitmix64Of(uniqSeed ^ splitmix64Of(n));
+}
+
 void fillReduceCPU(char* buf, uint64_t len, uint64_t firstChunk, uint64_t chunkBytes,
                    uint64_t randBytes, int dedupePct, uint64_t pool, uint64_t uniqSeed,
                    uint64_t poolSeed)
@@ -130,9 +138,7 @@ void fillReduceCPU(char* buf, uint64_t len, uint64_t firstChunk, uint64_t chunkB
     for (uint64_t pos = 0; pos < len; pos += chunkBytes, n++) {
         const uint64_t chunkLen = std::min(chunkBytes, len - pos);
         const uint64_t randLen = std::min(randBytes, chunkLen);
-        const bool dup = ((n + 1) * d) / 100 > (n * d) / 100;
-        const uint64_t key = dup ? splitmix64Of(poolSeed + (splitmix64Of(uniqSeed ^ n) % pool))
-                                 : splitmix64Of(uniqSeed ^ splitmix64Of(n));
+        const uint64_t key = reduceKeyCPU(n, d, pool, uniqSeed, poolSeed);
         for (uint64_t o = 0; o < randLen; o += 8) {
             const uint64_t v = splitmix64Of(key + (o / 8) * GOLD);
             std::memcpy(buf + pos + o, &v, std::min<uint64_t>(8, randLen - o));
@@ -148,6 +154,42 @@ ReduceSeeds reduceSeeds(uint64_t benchSeed, int phaseSeq, int globalRank)
     s.uniq = splitmix64Of(phaseSeed ^ (0xD1B54A32D192ED03ULL * (uint64_t)(globalRank + 1)));
     s.pool = splitmix64Of(benchSeed ^ 0x5DED0C0DE5EED001ULL);
     return s;
+}
+
+GpuVerifyResult verifyReduceCPU(const char* buf, uint64_t len, uint64_t fileOff,
+                                uint64_t firstChunk, uint64_t chunkBytes, uint64_t randBytes,
+                                int dedupePct, uint64_t pool, uint64_t uniqSeed,
+                                uint64_t poolSeed)
+{
+    constexpr uint64_t GOLD = 0x9E3779B97F4A7C15ULL;
+    GpuVerifyResult r{0, UINT64_MAX};
+    uint64_t n = firstChunk;
+    for (uint64_t pos = 0; pos < len; pos += chunkBytes, n++) {
+        const uint64_t chunkLen = std::min(chunkBytes, len - pos);
+        const uint64_t key = reduceKeyCPU(n, (uint64_t)dedupePct, pool, uniqSeed, poolSeed);
+        for (uint64_t o = 0; o < chunkLen; o += 8) {
+            const uint64_t want = (o < randBytes) ? splitmix64Of(key + (o / 8) * GOLD) : 0;
+            if (std::memcmp(buf + pos + o, &want, std::min<uint64_t>(8, chunkLen - o))) {
+                r.numMismatches++;
+                if (r.firstBadFileOffset == UINT64_MAX) r.firstBadFileOffset = fileOff + pos + o;
+            }
+        }
+    }
+    return r;
+}
+
+ReduceSeeds reduceVerifySeeds(uint64_t salt, uint64_t fileKey)
+{
+    ReduceSeeds s;
+    s.uniq = splitmix64Of(splitmix64Of(salt ^ REDUCE_VERIFY_UNIQ_XOR) +
+                          fileKey * 0x9E3779B97F4A7C15ULL);
+    s.pool = splitmix64Of(salt ^ REDUCE_VERIFY_POOL_XOR);
+    return s;
+}
+
+uint64_t reduceDirFileKey(uint64_t rank, uint64_t dir, uint64_t file)
+{
+    return splitmix64Of(splitmix64Of(splitmix64Of(rank + 1) ^ dir) ^ file);
 }
 
 void fillChecksumMixCPU(char* buf, uint64_t len, uint64_t fileOff, uint64_t salt,
@@ -801,6 +843,25 @@ void Worker::preWriteFill(int slot, uint64_t len, uint64_t fileOff)
         return;
     }
 
+    if (eng.reduceVerify) {
+        // --dedupeverify: the chunks that the file offset names, with the
+        // seeds of the slot's file; no worker state
+        const ReduceSeeds& seed = slotReduceSeed[slot];
+        const uint64_t first = fileOff / cfg.dedupeChunk;
+        if (gpu && (len % 16 == 0)) {
+            gpu->fillReduceDev(slot, len, first, cfg.dedupeChunk, eng.reduceRandBytes,
+                               cfg.dedupePct, REDUCE_POOL_CHUNKS, seed.uniq, seed.pool);
+            return;
+        }
+        fillReduceCPU(buf, len, first, cfg.dedupeChunk, eng.reduceRandBytes, cfg.dedupePct,
+                      REDUCE_POOL_CHUNKS, seed.uniq, seed.pool);
+        if (gpu) {
+            gpu->copyH2DAsync(slot, len);
+            gpu->syncStream();
+        }
+        return;
+    }
+
     if (eng.reduce) {
         // --dedupepct / --compresspct: the next ceil(len / chunk) chunks of
         // this worker's sequence, whatever the file offset
@@ -850,8 +911,7 @@ void Worker::preWriteFill(int slot, uint64_t len, uint64_t fileOff)
 
 void Worker::postReadCheck(int slot, uint64_t len, uint64_t fileOff)
 {
-    const auto& cfg = eng.cfg;
-    if (cfg.verifySalt < 0) return;
+    if (!eng.dataVerify) return;
 
     if (gpu && (fileOff % 8 == 0) && (len % 16 == 0)) {
         gpuVerifyAsync(slot, len, fileOff);
@@ -859,7 +919,21 @@ void Worker::postReadCheck(int slot, uint64_t len, uint64_t fileOff)
         return;
     }
 
-    cpuVerify(hostBufs[slot], len, fileOff);
+    cpuVerify(slot, hostBufs[slot], len, fileOff);
+}
+
+void Worker::setSlotFileKey(int slot, uint64_t fileKey)
+{
+    if (!eng.reduceVerify) return;
+    if (slotReduceSeed.size() < hostBufs.size()) slotReduceSeed.resize(hostBufs.size());
+    slotReduceSeed[slot] = reduceVerifySeeds((uint64_t)eng.cfg.reduceVerifySalt, fileKey);
+}
+
+void Worker::setAllSlotFileKeys(uint64_t fileKey)
+{
+    if (!eng.reduceVerify) return;
+    slotReduceSeed.assign(hostBufs.size(),
+                          reduceVerifySeeds((uint64_t)eng.cfg.reduceVerifySalt, fileKey));
 }
 
 // The three verify steps of every read path, in their plain, --verifymixpct
@@ -870,6 +944,13 @@ void Worker::postReadCheck(int slot, uint64_t len, uint64_t fileOff)
 void Worker::gpuVerifyAsync(int slot, uint64_t len, uint64_t fileOff)
 {
     const auto& cfg = eng.cfg;
+    if (eng.reduceVerify) {
+        const ReduceSeeds& seed = slotReduceSeed[slot];
+        gpu->verifyReduceDevAsync(slot, len, fileOff, fileOff / cfg.dedupeChunk,
+                                  cfg.dedupeChunk, eng.reduceRandBytes, cfg.dedupePct,
+                                  REDUCE_POOL_CHUNKS, seed.uniq, seed.pool);
+        return;
+    }
     const uint64_t salt = (uint64_t)cfg.verifySalt;
     if (cfg.verifyDiag) {
         if (eng.verifyMix)
@@ -913,9 +994,20 @@ void Worker::gpuVerifyDropStale()
     if (eng.cfg.verifyDiag) (void)gpu->fetchVerifyDiag();
 }
 
-void Worker::cpuVerify(const char* buf, uint64_t len, uint64_t fileOff)
+void Worker::cpuVerify(int slot, const char* buf, uint64_t len, uint64_t fileOff)
 {
     const auto& cfg = eng.cfg;
+    if (eng.reduceVerify) {
+        const ReduceSeeds& seed = slotReduceSeed[slot];
+        GpuVerifyResult r = verifyReduceCPU(buf, len, fileOff, fileOff / cfg.dedupeChunk,
+                                            cfg.dedupeChunk, eng.reduceRandBytes, cfg.dedupePct,
+                                            REDUCE_POOL_CHUNKS, seed.uniq, seed.pool);
+        if (r.numMismatches)
+            throw WorkerError("Data verification failed. First bad file offset: " +
+                              std::to_string(r.firstBadFileOffset) +
+                              "; mismatching 8-byte words: " + std::to_string(r.numMismatches));
+        return;
+    }
     const uint64_t salt = (uint64_t)cfg.verifySalt;
     std::string diagnosis;
     if (cfg.verifyDiag) {
@@ -1097,7 +1189,7 @@ void Worker::fileModeBlocks(bool isWrite)
                               !eng.opsLog.isEnabled(); // tracing needs per-op hooks
     if (gpuPipelined) {
         constexpr uint64_t VERIFY_FETCH_INTERVAL = 64;
-        const bool doVerify = cfg.verifySalt >= 0;
+        const bool doVerify = eng.dataVerify;
         const bool lat = cfg.measureLat;
         const int nSlots = (int)hostBufs.size();
         std::vector<char> slotBusy(nSlots, 0);
@@ -1128,6 +1220,7 @@ void Worker::fileModeBlocks(bool isWrite)
                     if ((opCount++ % INTERRUPT_CHECK_INTERVAL) == 0) checkInterrupt();
                     rateLimiter.wait(ioLen);
                     if (slotBusy[slot]) gpu->waitSlotEvent(slot);
+                    setSlotFileKey(slot, fileIdx);
                     preWriteFill(slot, ioLen, inFileOff);
                     if (lat) gpu->recordTimedStart(slot);
                     gpu->copyD2HAsync(slot, ioLen);
@@ -1272,6 +1365,7 @@ void Worker::fileModeBlocks(bool isWrite)
                 gpu->copyH2DAsync(slot, ioLen);
                 if (lat) gpu->recordTimedEnd(slot);
                 if (doVerify) {
+                    setSlotFileKey(slot, fileIdx);
                     if ((inFileOff % 8 == 0) && (ioLen % 16 == 0)) {
                         gpuVerifyAsync(slot, ioLen, inFileOff);
                         if (++sinceFetch >= VERIFY_FETCH_INTERVAL) {
@@ -1279,7 +1373,7 @@ void Worker::fileModeBlocks(bool isWrite)
                             sinceFetch = 0;
                         }
                     } else { // odd tail: CPU check of the host copy
-                        cpuVerify(hostBufs[slot], ioLen, inFileOff);
+                        cpuVerify(slot, hostBufs[slot], ioLen, inFileOff);
                     }
                 }
                 gpu->recordSlotEvent(slot);
@@ -1325,6 +1419,7 @@ void Worker::fileModeBlocks(bool isWrite)
 
         auto t0 = lat ? Clock::now() : Clock::time_point();
 
+        setSlotFileKey(0, fileIdx);
         ssize_t res = blockIO(blockWrite, fg.fds[fileIdx], 0, ioLen, inFileOff,
                               mg.base(fileIdx), &cfg.paths[fileIdx]);
         if (res < 0)
@@ -1361,7 +1456,7 @@ void Worker::fileModeBlocksGpuMmap(bool isWrite)
     const uint64_t bs = cfg.blockSize;
     const size_t numFiles = cfg.paths.size();
     const uint64_t numBlocksPerFile = (fileSize + bs - 1) / bs;
-    const bool doVerify = cfg.verifySalt >= 0;
+    const bool doVerify = eng.dataVerify;
     const bool lat = cfg.measureLat;
 
     // registered mappings (cached in the engine across phases)
@@ -1450,6 +1545,7 @@ void Worker::fileModeBlocksGpuMmap(bool isWrite)
         if (lat && gpu->timedPairActive(slot))
             addIoLat(gpu->timedElapsedUSec(slot));
 
+        setSlotFileKey(slot, fileIdx);
         if (isWrite) {
             // fill the HBM slot, then DMA into the mapped file pages
             preWriteFill(slot, ioLen, inFileOff);
@@ -1467,7 +1563,7 @@ void Worker::fileModeBlocksGpuMmap(bool isWrite)
                     sinceFetch = 0;
                 }
             } else if (doVerify) { // odd tail: check the mapped pages directly
-                cpuVerify(bases[fileIdx] + inFileOff, ioLen, inFileOff);
+                cpuVerify(slot, bases[fileIdx] + inFileOff, ioLen, inFileOff);
             }
         }
 
@@ -1572,7 +1668,7 @@ void Worker::fileModeBlocksUring(bool isWrite)
     // half-ring batching (5.1M vs 3.4M IOPS warm), so batching here is
     // opt-in (EB_GPU_URING_BATCH=1) — unlike the sync path where it wins
     const int gpuBatch = gpu ? gpuBatchSlots(bs) : 1;
-    const bool batchedRead = gpu && !isWrite && cfg.verifySalt < 0 &&
+    const bool batchedRead = gpu && !isWrite && !eng.dataVerify &&
                              gpuBatch >= 2 && depth >= 4 &&
                              getenv("EB_GPU_URING_BATCH");
     if (getenv("EB_DEBUG_PATH"))
@@ -1702,6 +1798,7 @@ void Worker::fileModeBlocksUring(bool isWrite)
             gpu->waitSlotEvent(slot);
             slotHasCopy[slot] = false;
         }
+        setSlotFileKey(slot, fileIdx);
         if (blockWrite) {
             preWriteFill(slot, ioLen, inFileOff);
             if (gpu) {
@@ -1758,7 +1855,7 @@ void Worker::fileModeBlocksUring(bool isWrite)
             if (!wasWrite) {
                 if (gpu) {
                     gpu->copyH2DAsync(slot, st.len);
-                    if (cfg.verifySalt >= 0 && !isWrite) {
+                    if (eng.dataVerify && !isWrite) {
                         gpu->syncStream();
                         postReadCheck(slot, st.len, st.inFileOff);
                     } else { // pipelined: wait only when the slot is reused
@@ -1988,7 +2085,7 @@ void Worker::uringFileBlocks(FileUring& u, int fd, const std::string& path,
                 const bool check = !phaseIsWrite || checkMixReads;
                 if (gpu) {
                     gpu->copyH2DAsync(slot, st.len);
-                    if (cfg.verifySalt >= 0 && check) {
+                    if (eng.dataVerify && check) {
                         gpu->syncStream();
                         postReadCheck(slot, st.len, st.off);
                     } else { // pipelined: wait only when the slot is reused
@@ -2030,7 +2127,7 @@ bool Worker::dirModeSmallFileUring(bool isWrite)
     const uint64_t numDirs = haveSubdirs ? cfg.numDirs : 1;
     const int dirRank = cfg.dirSharing ? 0 : globalRank;
     const int depth = std::min<int>(cfg.ioDepth, (int)hostBufs.size());
-    const bool doVerify = cfg.verifySalt >= 0;
+    const bool doVerify = eng.dataVerify;
 
     int openFlags = isWrite ? (O_CREAT | O_WRONLY) : O_RDONLY;
     if (cfg.directIO) openFlags |= O_DIRECT;
@@ -2086,6 +2183,7 @@ bool Worker::dirModeSmallFileUring(bool isWrite)
         st.path = cfg.paths[pathIdx] + "/" + rel;
         st.failed = false;
         if (lat) st.entryStart = Clock::now();
+        setSlotFileKey(s, reduceDirFileKey((uint64_t)globalRank, d, f));
 
         if (isWrite && fileSize) {
             if (gpu && slotHasCopy[s]) { // prior read staged from this buf
@@ -2401,6 +2499,7 @@ void Worker::dirModeFiles(Phase phase)
                         if (!gen) gen = makeOffsetGen(0, fileSize);
                         else gen->reset(0, fileSize);
 
+                        setAllSlotFileKeys(reduceDirFileKey((uint64_t)globalRank, d, f));
                         if (useUring) {
                             uringFileBlocks(*fu, fd, full, *gen, isWrite,
                                             rwMixActive,
@@ -2674,6 +2773,7 @@ void Worker::customTreeFiles(Phase phase)
                         else gen->reset(rangeStart, rangeLen);
                         og = gen.get();
                     }
+                    setAllSlotFileKeys(i); // the file's index in the tree file list
                     if (useUring) {
                         uringFileBlocks(*fu, fd, full, *og, isWrite,
                                         /*rwMixActive=*/false,
@@ -3024,6 +3124,7 @@ void Worker::threadMain()
             if (eng.currentPhase == Phase::WRITE || eng.currentPhase == Phase::READ ||
                 eng.currentPhase == Phase::NETBENCH)
                 allocBuffers();
+            if (eng.reduceVerify) slotReduceSeed.resize(hostBufs.size());
 
             rateLimiter.init((eng.currentPhase == Phase::WRITE && !isDedicatedReader)
                                  ? eng.cfg.limitWriteBps
@@ -3086,6 +3187,28 @@ Engine::Engine(EngineConfig cfgIn) : cfg(std::move(cfgIn))
         reduce = true;
         reduceRandBytes = (cfg.dedupeChunk * (uint64_t)(100 - cfg.compressPct) / 100) & ~15ULL;
     }
+
+    if (cfg.reduceVerifySalt < -1)
+        throw std::invalid_argument("reduce_verify_salt must be >= 0 (or -1 for unset)");
+    if (cfg.reduceVerifySalt >= 0) {
+        if (!reduce)
+            throw std::invalid_argument(
+                "reduce_verify_salt requires a non-zero dedupe_pct or compress_pct");
+        if (cfg.verifyMixPct >= 0)
+            throw std::invalid_argument(
+                "reduce_verify_salt cannot be used together with verify_mix_pct");
+        if (cfg.verifyDiag)
+            throw std::invalid_argument(
+                "reduce_verify_salt cannot be used together with verify_diag");
+        if (cfg.random && !cfg.randAligned)
+            throw std::invalid_argument(
+                "reduce_verify_salt cannot be used with unaligned random offsets");
+        if (!cfg.blockSize || cfg.blockSize % cfg.dedupeChunk)
+            throw std::invalid_argument(
+                "reduce_verify_salt requires a block size that is a multiple of dedupe_chunk");
+        reduceVerify = true;
+    }
+    dataVerify = cfg.verifySalt >= 0 || reduceVerify;
 }
 
 Engine::~Engine()

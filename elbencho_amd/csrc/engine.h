@@ -69,6 +69,9 @@ struct EngineConfig {
     int dedupePct = 0;
     int compressPct = 0;
     uint64_t dedupeChunk = 4096;
+    // --dedupeverify SALT: reduce pattern keyed by (SALT, file, file offset)
+    // and checked on read; < 0 off. Needs dedupePct / compressPct > 0.
+    int64_t reduceVerifySalt = -1;
     std::string blockVarAlgo = "fast";
     std::string randAlgo = "fast";
 
@@ -258,7 +261,12 @@ private:
     void gpuVerifyAsync(int slot, uint64_t len, uint64_t fileOff);
     void gpuVerifyFetch();     // throws WorkerError on a mismatch
     void gpuVerifyDropStale(); // forget what a failed phase left unfetched
-    void cpuVerify(const char* buf, uint64_t len, uint64_t fileOff);
+    // slot: the I/O slot the block belongs to (--dedupeverify takes the file
+    // key from it); buf need not be that slot's host buffer
+    void cpuVerify(int slot, const char* buf, uint64_t len, uint64_t fileOff);
+    // --dedupeverify: the seeds of the file that the slot's block belongs to
+    void setSlotFileKey(int slot, uint64_t fileKey);
+    void setAllSlotFileKeys(uint64_t fileKey);
     ssize_t blockIO(bool isWrite, int fd, int slot, uint64_t len, uint64_t fileOff,
                     char* mmapBase = nullptr, const std::string* path = nullptr);
     void verifyDirectReadback(int fd, int slot, uint64_t len, uint64_t fileOff);
@@ -282,6 +290,9 @@ private:
     // generates (0 at the start of a phase and of every --infloop pass)
     uint64_t reduceNextChunk = 0;
     ReduceSeeds reduceSeed;
+    // --dedupeverify: per I/O slot, the seeds of the file whose block the slot
+    // holds (several files are in flight per worker on the io_uring paths)
+    std::vector<ReduceSeeds> slotReduceSeed;
     RateLimiter rateLimiter;
 };
 
@@ -377,6 +388,10 @@ public:
     // random, the rest zero
     bool reduce = false;
     uint64_t reduceRandBytes = 0;
+    // --dedupeverify on (then reduce is on too); dataVerify: reads are checked,
+    // by --verify or by --dedupeverify
+    bool reduceVerify = false;
+    bool dataVerify = false;
 
     // GPU contexts cached across phases (hipMalloc + pinned allocs are
     // expensive; reusing them keeps phase setup off the measured path)
@@ -442,6 +457,28 @@ void fillReduceCPU(char* buf, uint64_t len, uint64_t firstChunk, uint64_t chunkB
                    uint64_t poolSeed);
 // the seeds a worker uses in the phase with sequence number phaseSeq
 ReduceSeeds reduceSeeds(uint64_t benchSeed, int phaseSeq, int globalRank);
+
+// --dedupeverify: the content of a file is a function of (salt, file key, file
+// offset) alone. The block at file offset o (a multiple of chunkBytes) holds
+// chunks o / chunkBytes, o / chunkBytes + 1, ... of the pattern above with
+//   poolSeed = mix(salt ^ REDUCE_VERIFY_POOL_XOR)            (the same for every file)
+//   uniqSeed = mix(mix(salt ^ REDUCE_VERIFY_UNIQ_XOR) + fileKey * GOLD)
+// The file key is the path's index in file/bdev mode, the file's index in the
+// tree file list in custom-tree mode and reduceDirFileKey in directory mode.
+constexpr uint64_t REDUCE_VERIFY_POOL_XOR = 0xA0761D6478BD642FULL;
+constexpr uint64_t REDUCE_VERIFY_UNIQ_XOR = 0xE7037ED1A0B428DBULL;
+ReduceSeeds reduceVerifySeeds(uint64_t salt, uint64_t fileKey);
+// key of r{rank}/d{dir}/r{rank}-f{file}: mix(mix(mix(rank + 1) ^ dir) ^ file)
+uint64_t reduceDirFileKey(uint64_t rank, uint64_t dir, uint64_t file);
+// Compares buf, which lies at file offset fileOff, with what fillReduceCPU
+// writes for the same arguments (any len; a cut last word is compared over
+// the bytes it has). Returns the number of mismatching 8-byte words and the
+// file offset of the first one (fileOff + 8 * word index), UINT64_MAX if none:
+// the result of GpuCtx::verifyReduceDev.
+GpuVerifyResult verifyReduceCPU(const char* buf, uint64_t len, uint64_t fileOff,
+                                uint64_t firstChunk, uint64_t chunkBytes, uint64_t randBytes,
+                                int dedupePct, uint64_t pool, uint64_t uniqSeed,
+                                uint64_t poolSeed);
 
 // --verifydiag on a host buffer: the contract of GpuVerifyDiag (gpu.h), added
 // into `acc` (a default-constructed record is empty). Any alignment; a word

@@ -77,6 +77,12 @@ double gpuVerifyBenchGBs(uint64_t len, int iters, bool lds, int dev);
 double gpuMixBenchGBs(uint64_t len, int iters, int dev, uint64_t blockSize, uint64_t mixLen,
                       bool fill, bool plainFill);
 
+// Micro-bench of ebVerifyReduceKernel (GB/s) on one len-byte buffer of clean
+// pattern data (chunk 0 onwards, pool of 256), timed as gpuMixBenchGBs times
+// its verify. Requires len % 16 == 0 and fillReduceDev's geometry.
+double gpuReduceVerifyBenchGBs(uint64_t len, int iters, int dev, uint64_t chunkBytes,
+                               uint64_t randBytes, int dedupePct);
+
 // gpuVerifyBenchGBs for ebVerifyDiagKernel: same buffer, same clean data.
 double gpuVerifyDiagBenchGBs(uint64_t len, int iters, int dev);
 
@@ -232,6 +238,21 @@ public:
     void fillReduceDev(int slot, uint64_t len, uint64_t firstChunk, uint64_t chunkBytes,
                        uint64_t randBytes, int dedupePct, uint64_t pool, uint64_t uniqSeed,
                        uint64_t poolSeed);
+
+    // --dedupeverify (ebVerifyReduceKernel): compare the slot's first len bytes,
+    // which lie at file offset fileOff, with what fillReduceDev writes for the
+    // same arguments. fillReduceDev's argument contract, and fileOff % 8 == 0,
+    // else std::invalid_argument; len == 0 launches nothing. The mismatching
+    // 8-byte words and the lowest bad file offset (fileOff + byte index) add
+    // into the counters of verifyChecksumDevAsync, so fetchVerifyResult()
+    // serves it; verifyReduceDev fetches at once (synchronizes).
+    void verifyReduceDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t firstChunk,
+                              uint64_t chunkBytes, uint64_t randBytes, int dedupePct,
+                              uint64_t pool, uint64_t uniqSeed, uint64_t poolSeed);
+    GpuVerifyResult verifyReduceDev(int slot, uint64_t len, uint64_t fileOff,
+                                    uint64_t firstChunk, uint64_t chunkBytes,
+                                    uint64_t randBytes, int dedupePct, uint64_t pool,
+                                    uint64_t uniqSeed, uint64_t poolSeed);
 
     // --- CRC-32 / CRC-32C of a slot's first len bytes, computed in HBM ---
     // Everything these need (byte tables, the partials array) is allocated

@@ -208,12 +208,40 @@ __device__ __forceinline__ uint64_t d_uniform64(uint64_t v)
     return ((uint64_t)hi << 32) | lo;
 }
 
-// One workgroup step writes 256 consecutive 16 B elements = 4 KiB. With
-// chunks of 4 KiB and more (vecShift >= 8) those lie in one chunk, so the
-// chunk number and its key depend on the step alone: they are uniform over
-// the workgroup and cost one computation per chunk and wave, not per element.
-// Smaller chunks compute the key per lane. Lanes in the zero tail of a chunk
-// skip the hashing. No LDS, no atomics.
+// The 16 B element with index idx (in workgroup step `step` = idx / 256) of a
+// buffer that starts with chunk firstChunk: what the fill writes and what the
+// verify expects. With chunks of 4 KiB and more (vecShift >= 8) the 256
+// elements of a step lie in one chunk, so the chunk number and its key depend
+// on the step alone: they are uniform over the workgroup and cost one
+// computation per chunk and wave, not per element. Smaller chunks compute the
+// key per lane. Lanes in the zero tail of a chunk skip the hashing.
+__device__ __forceinline__ ulonglong2 d_reduceElem(uint64_t step, uint64_t idx,
+                                                   uint64_t firstChunk, uint32_t firstMod,
+                                                   uint32_t vecShift, uint64_t randVec2,
+                                                   uint32_t dedupePct, uint64_t pool,
+                                                   uint64_t uniqSeed, uint64_t poolSeed)
+{
+    const uint64_t pos = idx & ((1ULL << vecShift) - 1); // element within its chunk
+    ulonglong2 val;
+    val.x = 0;
+    val.y = 0;
+    if (pos < randVec2) {
+        uint64_t key; // two calls: the first one's arguments are all uniform
+        if (vecShift >= 8)
+            key = d_uniform64(d_reduceKey(firstChunk, firstMod, step >> (vecShift - 8),
+                                          dedupePct, pool, uniqSeed, poolSeed));
+        else
+            key = d_reduceKey(firstChunk, firstMod, idx >> vecShift, dedupePct, pool,
+                              uniqSeed, poolSeed);
+        const uint64_t s0 = key + pos * 2 * 0x9E3779B97F4A7C15ULL;
+        val.x = d_mix64(s0);
+        val.y = d_mix64(s0 + 0x9E3779B97F4A7C15ULL);
+    }
+    return val;
+}
+
+// One workgroup step writes 256 consecutive 16 B elements = 4 KiB, each one
+// d_reduceElem of its index. No LDS, no atomics.
 __global__ __launch_bounds__(256) void ebFillReduceKernel(
     ulonglong2* __restrict__ buf, uint64_t nVec2, uint64_t firstChunk, uint32_t firstMod,
     uint32_t vecShift,  // log2(16 B elements per chunk)
@@ -221,26 +249,62 @@ __global__ __launch_bounds__(256) void ebFillReduceKernel(
     uint32_t dedupePct, uint64_t pool, uint64_t uniqSeed, uint64_t poolSeed)
 {
     const uint64_t nSteps = (nVec2 + 255) / 256;
-    const uint64_t vecMask = (1ULL << vecShift) - 1;
     for (uint64_t step = blockIdx.x; step < nSteps; step += gridDim.x) {
         const uint64_t idx = step * 256 + threadIdx.x;
-        const uint64_t pos = idx & vecMask; // element within its chunk
-        ulonglong2 val;
-        val.x = 0;
-        val.y = 0;
-        if (pos < randVec2) {
-            uint64_t key; // two calls: the first one's arguments are all uniform
-            if (vecShift >= 8)
-                key = d_uniform64(d_reduceKey(firstChunk, firstMod, step >> (vecShift - 8),
-                                              dedupePct, pool, uniqSeed, poolSeed));
-            else
-                key = d_reduceKey(firstChunk, firstMod, idx >> vecShift, dedupePct, pool,
-                                  uniqSeed, poolSeed);
-            const uint64_t s0 = key + pos * 2 * 0x9E3779B97F4A7C15ULL;
-            val.x = d_mix64(s0);
-            val.y = d_mix64(s0 + 0x9E3779B97F4A7C15ULL);
-        }
+        const ulonglong2 val = d_reduceElem(step, idx, firstChunk, firstMod, vecShift, randVec2,
+                                            dedupePct, pool, uniqSeed, poolSeed);
         if (idx < nVec2) buf[idx] = val;
+    }
+}
+
+// --dedupeverify: the read side of the pattern above. Same geometry as the
+// fill (one workgroup step = 256 consecutive 16 B elements, grid-stride over
+// steps): one 16 B load per element, compared with d_reduceElem of its index.
+// The buffer's byte 0 lies at file offset fileOff. Mismatching 8-byte words
+// are counted (.x and .y separately) and the lowest bad file offset is kept;
+// one wave64 reduction after the loop, then one atomicAdd / atomicMin per
+// wave that saw a bad word, into the counters of ebVerifyChecksumKernel
+// (out[0] += count, out[1] = min offset). No LDS; nothing at or past nVec2 is
+// read.
+__global__ __launch_bounds__(256) void ebVerifyReduceKernel(
+    const ulonglong2* __restrict__ buf, uint64_t nVec2, uint64_t fileOff, uint64_t firstChunk,
+    uint32_t firstMod, uint32_t vecShift, uint64_t randVec2, uint32_t dedupePct, uint64_t pool,
+    uint64_t uniqSeed, uint64_t poolSeed, unsigned long long* __restrict__ out)
+{
+    const uint64_t nSteps = (nVec2 + 255) / 256;
+
+    unsigned long long localBad = 0;
+    unsigned long long localFirst = ~0ULL;
+
+    for (uint64_t step = blockIdx.x; step < nSteps; step += gridDim.x) {
+        const uint64_t idx = step * 256 + threadIdx.x;
+        if (idx < nVec2) {
+            const ulonglong2 v = buf[idx]; // 16 B/lane coalesced read
+            const ulonglong2 exp = d_reduceElem(step, idx, firstChunk, firstMod, vecShift,
+                                                randVec2, dedupePct, pool, uniqSeed, poolSeed);
+            const uint64_t off0 = fileOff + idx * 16;
+            if (v.x != exp.x) {
+                localBad++;
+                if (off0 < localFirst) localFirst = off0;
+            }
+            if (v.y != exp.y) {
+                localBad++;
+                if (off0 + 8 < localFirst) localFirst = off0 + 8;
+            }
+        }
+    }
+
+    // wave64 reduction: sum mismatches and min first-bad across lanes
+#pragma unroll
+    for (int delta = 32; delta > 0; delta >>= 1) {
+        localBad += __shfl_down(localBad, delta, 64);
+        unsigned long long other = __shfl_down(localFirst, delta, 64);
+        if (other < localFirst) localFirst = other;
+    }
+
+    if ((threadIdx.x & 63) == 0 && localBad) {
+        atomicAdd(&out[0], localBad);
+        atomicMin(&out[1], localFirst);
     }
 }
 
@@ -1573,6 +1637,36 @@ void GpuCtx::fillReduceDev(int slot, uint64_t len, uint64_t firstChunk, uint64_t
     HIP_CHECK(hipGetLastError());
 }
 
+void GpuCtx::verifyReduceDevAsync(int slot, uint64_t len, uint64_t fileOff, uint64_t firstChunk,
+                                  uint64_t chunkBytes, uint64_t randBytes, int dedupePct,
+                                  uint64_t pool, uint64_t uniqSeed, uint64_t poolSeed)
+{
+    requireAligned("verifyReduceDev", len, 16, fileOff);
+    requireReduceGeometry("verifyReduceDev", firstChunk, chunkBytes, randBytes, dedupePct, pool);
+    if (len > impl->slotStride)
+        throw std::invalid_argument("verifyReduceDev: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    uint64_t nVec2 = len / 16;
+    if (!nVec2) return;
+    hipLaunchKernelGGL(ebVerifyReduceKernel, gridForBytes(nVec2), dim3(256), 0, impl->stream,
+                       (const ulonglong2*)impl->devBufs[slot], nVec2, fileOff, firstChunk,
+                       (uint32_t)(firstChunk % 100), (uint32_t)__builtin_ctzll(chunkBytes / 16),
+                       randBytes / 16, (uint32_t)dedupePct, pool, uniqSeed, poolSeed,
+                       impl->verifyOutDev);
+    HIP_CHECK(hipGetLastError());
+    impl->verifyDirty = true;
+}
+
+GpuVerifyResult GpuCtx::verifyReduceDev(int slot, uint64_t len, uint64_t fileOff,
+                                        uint64_t firstChunk, uint64_t chunkBytes,
+                                        uint64_t randBytes, int dedupePct, uint64_t pool,
+                                        uint64_t uniqSeed, uint64_t poolSeed)
+{
+    verifyReduceDevAsync(slot, len, fileOff, firstChunk, chunkBytes, randBytes, dedupePct, pool,
+                         uniqSeed, poolSeed);
+    return fetchVerifyResult();
+}
+
 // --- CRC-32 / CRC-32C in HBM ---
 
 uint64_t gpuCrcTileBytes() { return CRC_TILE_BYTES; }
@@ -1904,6 +1998,62 @@ double gpuMixBenchGBs(uint64_t len, int iters, int dev, uint64_t blockSize, uint
     (void)hipFree(buf);
     (void)hipFree(out);
 
+    return (double)len * iters / (ms / 1000.0) / 1e9;
+}
+
+double gpuReduceVerifyBenchGBs(uint64_t len, int iters, int dev, uint64_t chunkBytes,
+                               uint64_t randBytes, int dedupePct)
+{
+    requireAligned("gpuReduceVerifyBenchGBs", len, 16);
+    requireReduceGeometry("gpuReduceVerifyBenchGBs", 0, chunkBytes, randBytes, dedupePct, 256);
+    if (!len || iters < 1)
+        throw std::invalid_argument("gpuReduceVerifyBenchGBs: nothing to run");
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t nVec2 = len / 16;
+    ulonglong2* buf = nullptr;
+    unsigned long long* out = nullptr;
+    HIP_CHECK(hipMalloc(&buf, len));
+    HIP_CHECK(hipMalloc(&out, 2 * sizeof(unsigned long long)));
+    HIP_CHECK(hipMemset(out, 0, 2 * sizeof(unsigned long long)));
+
+    hipStream_t s;
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    const uint32_t vecShift = (uint32_t)__builtin_ctzll(chunkBytes / 16);
+
+    // the data the verify reads (clean: no atomics in the timed loop)
+    hipLaunchKernelGGL(ebFillReduceKernel, gridForBytes(nVec2), dim3(256), 0, s, buf, nVec2,
+                       (uint64_t)0, 0u, vecShift, randBytes / 16, (uint32_t)dedupePct,
+                       (uint64_t)256, (uint64_t)42, (uint64_t)43);
+    auto launch = [&] {
+        hipLaunchKernelGGL(ebVerifyReduceKernel, gridForBytes(nVec2), dim3(256), 0, s, buf,
+                           nVec2, (uint64_t)0, (uint64_t)0, 0u, vecShift, randBytes / 16,
+                           (uint32_t)dedupePct, (uint64_t)256, (uint64_t)42, (uint64_t)43, out);
+    };
+
+    launch(); // warmup
+    launch();
+    HIP_CHECK(hipStreamSynchronize(s));
+
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    HIP_CHECK(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; i++) launch();
+    HIP_CHECK(hipEventRecord(e1, s));
+    HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+
+    unsigned long long bad = 0;
+    HIP_CHECK(hipMemcpy(&bad, out, sizeof(bad), hipMemcpyDeviceToHost));
+
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(buf);
+    (void)hipFree(out);
+
+    if (bad) throw std::runtime_error("gpuReduceVerifyBenchGBs: the clean buffer did not verify");
     return (double)len * iters / (ms / 1000.0) / 1e9;
 }
 

@@ -148,6 +148,7 @@ EngineConfig configFromDict(const py::dict& d)
     c.dedupePct = (int)getI("dedupe_pct", 0);
     c.compressPct = (int)getI("compress_pct", 0);
     c.dedupeChunk = getU64("dedupe_chunk", 4096);
+    c.reduceVerifySalt = getI("reduce_verify_salt", -1);
     c.randAlgo = getS("rand_algo", "balanced_single");
     if (d.contains("gpu_ids")) c.gpuIDs = d["gpu_ids"].cast<std::vector<int>>();
     c.gpuPinnedHostBufs = getB("gpu_pinned", true);
@@ -290,6 +291,27 @@ PYBIND11_MODULE(_core, m)
         return py::make_tuple(s.uniq, s.pool);
     }, py::arg("bench_seed"), py::arg("phase_seq"), py::arg("rank"));
     m.attr("REDUCE_POOL_CHUNKS") = REDUCE_POOL_CHUNKS;
+
+    // --dedupeverify on the CPU: (mismatching 8-byte words, first bad file
+    // offset or 2^64-1) of data, which lies at file_off, against the pattern
+    // from chunk first_chunk on; the seeds of a file; the key of a dir-mode file
+    m.def("verify_reduce", [](py::bytes data, uint64_t fileOff, uint64_t firstChunk,
+                              uint64_t chunk, uint64_t randBytes, int dedupePct, uint64_t pool,
+                              uint64_t uniqSeed, uint64_t poolSeed) {
+        requireReduceArgs("verify_reduce", chunk, randBytes, dedupePct, pool);
+        std::string buf = data;
+        GpuVerifyResult r = verifyReduceCPU(buf.data(), buf.size(), fileOff, firstChunk, chunk,
+                                            randBytes, dedupePct, pool, uniqSeed, poolSeed);
+        return py::make_tuple(r.numMismatches, r.firstBadFileOffset);
+    }, py::arg("data"), py::arg("file_off"), py::arg("first_chunk"), py::arg("chunk"),
+       py::arg("rand_bytes"), py::arg("dedupe_pct"), py::arg("pool"), py::arg("uniq_seed"),
+       py::arg("pool_seed"));
+    m.def("reduce_verify_seeds", [](uint64_t salt, uint64_t fileKey) {
+        ReduceSeeds s = reduceVerifySeeds(salt, fileKey);
+        return py::make_tuple(s.uniq, s.pool);
+    }, py::arg("salt"), py::arg("file_key"));
+    m.def("reduce_dir_file_key", &reduceDirFileKey, py::arg("rank"), py::arg("dir"),
+          py::arg("file"));
 
     // --verifydiag on the CPU; block_size 0 selects the plain pattern
     m.def("verify_diag", [](py::bytes data, uint64_t fileOff, uint64_t salt,
@@ -814,6 +836,68 @@ PYBIND11_MODULE(_core, m)
        py::arg("dedupe_pct"), py::arg("pool"), py::arg("uniq_seed"), py::arg("pool_seed"),
        py::arg("dev") = 0, py::arg("pad") = 0, py::arg("sentinel") = 0xA5,
        py::arg("then_blockvar_seed") = py::none());
+
+    // --dedupeverify kernel: data goes into a one-slot context and its first
+    // verify_len bytes (default: all of it) are verified in HBM, so bytes
+    // behind verify_len lie directly behind the verified range in the slot.
+    m.def("gpu_verify_reduce", [](py::bytes data, uint64_t fileOff, uint64_t firstChunk,
+                                  uint64_t chunk, uint64_t randBytes, int dedupePct,
+                                  uint64_t pool, uint64_t uniqSeed, uint64_t poolSeed, int dev,
+                                  std::optional<uint64_t> verifyLen) {
+        std::string buf = data;
+        const uint64_t len = verifyLen ? *verifyLen : buf.size();
+        if (len > buf.size())
+            throw std::invalid_argument("gpu_verify_reduce: verify_len exceeds the data");
+        GpuCtx ctx(dev, 1, std::max<uint64_t>(buf.size(), 16), true);
+        std::memcpy(ctx.hostBuf(0), buf.data(), buf.size());
+        if (!buf.empty()) ctx.copyH2DAsync(0, buf.size());
+        ctx.syncStream();
+        GpuVerifyResult r = ctx.verifyReduceDev(0, len, fileOff, firstChunk, chunk, randBytes,
+                                                dedupePct, pool, uniqSeed, poolSeed);
+        return py::make_tuple(r.numMismatches, r.firstBadFileOffset);
+    }, py::arg("data"), py::arg("file_off"), py::arg("first_chunk"), py::arg("chunk"),
+       py::arg("rand_bytes"), py::arg("dedupe_pct"), py::arg("pool"), py::arg("uniq_seed"),
+       py::arg("pool_seed"), py::arg("dev") = 0, py::arg("verify_len") = py::none());
+
+    // One slot and one async launch per (data, file_off, first_chunk) item with
+    // no fetch in between; returns the results of two fetchVerifyResult calls.
+    m.def("gpu_verify_reduce_batch",
+          [](const std::vector<std::tuple<py::bytes, uint64_t, uint64_t>>& items, uint64_t chunk,
+             uint64_t randBytes, int dedupePct, uint64_t pool, uint64_t uniqSeed,
+             uint64_t poolSeed, int dev) {
+        if (items.empty()) throw std::invalid_argument("gpu_verify_reduce_batch: no items");
+        std::vector<std::string> bufs;
+        uint64_t maxLen = 16;
+        for (const auto& it : items) {
+            bufs.emplace_back(std::get<0>(it));
+            maxLen = std::max<uint64_t>(maxLen, bufs.back().size());
+        }
+        GpuCtx ctx(dev, (int)bufs.size(), maxLen, true);
+        for (size_t i = 0; i < bufs.size(); i++) {
+            std::memcpy(ctx.hostBuf((int)i), bufs[i].data(), bufs[i].size());
+            if (!bufs[i].empty()) ctx.copyH2DAsync((int)i, bufs[i].size());
+            ctx.verifyReduceDevAsync((int)i, bufs[i].size(), std::get<1>(items[i]),
+                                     std::get<2>(items[i]), chunk, randBytes, dedupePct, pool,
+                                     uniqSeed, poolSeed);
+        }
+        py::list out;
+        for (int k = 0; k < 2; k++) {
+            GpuVerifyResult r = ctx.fetchVerifyResult();
+            out.append(py::make_tuple(r.numMismatches, r.firstBadFileOffset));
+        }
+        return out;
+    }, py::arg("items"), py::arg("chunk"), py::arg("rand_bytes"), py::arg("dedupe_pct"),
+       py::arg("pool"), py::arg("uniq_seed"), py::arg("pool_seed"), py::arg("dev") = 0);
+
+    // like gpu_verify_mix_bench (clean data, GB/s) for ebVerifyReduceKernel
+    m.def("gpu_reduce_verify_bench_gbs",
+          [](uint64_t len, int iters, int dev, uint64_t chunk, uint64_t randBytes,
+             int dedupePct) {
+              py::gil_scoped_release rel;
+              return gpuReduceVerifyBenchGBs(len, iters, dev, chunk, randBytes, dedupePct);
+          },
+          py::arg("len"), py::arg("iters") = 50, py::arg("dev") = 0, py::arg("chunk") = 4096,
+          py::arg("rand_bytes") = 2048, py::arg("dedupe_pct") = 50);
 
     // Kernel micro-benchmark: bandwidth of the gfx950 fill/verify kernels and
     // the staging copies on one device buffer (GB/s, stream-synchronized).
