@@ -3409,6 +3409,25 @@ Engine::GpuSlotsSnapshot Engine::gpuSlots(int localRank)
     return snap;
 }
 
+std::vector<std::pair<uint64_t, bool>> Engine::gpuStreams()
+{
+    if (phaseRunning)
+        throw std::runtime_error("gpu_streams: a phase is running (call finish_phase first)");
+
+    std::vector<std::pair<uint64_t, bool>> out;
+    std::lock_guard<std::mutex> lk(gpuCacheMtx);
+    for (int r = 0; r < cfg.numThreads; r++) { // same lookup as gpuSlots
+        GpuCtx* ctx = nullptr;
+        if ((size_t)r < workers.size()) ctx = workers[r]->gpuCtx();
+        if (!ctx && (size_t)r < gpuCtxCache.size()) ctx = gpuCtxCache[r].get();
+        if (!ctx)
+            throw std::runtime_error("gpu_streams: worker " + std::to_string(r) +
+                                     " has no GPU context");
+        out.emplace_back(ctx->streamId(), ctx->streamShared());
+    }
+    return out;
+}
+
 std::vector<WorkerResult> Engine::finishPhase()
 {
     { // workers stay alive (parked at the gate); just wait for phase end

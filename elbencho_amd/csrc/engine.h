@@ -337,6 +337,12 @@ public:
     };
     GpuSlotsSnapshot gpuSlots(int localRank);
 
+    // Which HIP stream each local worker's context enqueues into (test/
+    // diagnostic hook): {GpuCtx::streamId(), GpuCtx::streamShared()} per local
+    // rank, contexts looked up as gpuSlots does. No device work. Throws while
+    // a phase is running and when a worker has no GPU context.
+    std::vector<std::pair<uint64_t, bool>> gpuStreams();
+
     // ---- shared state visible to workers ----
     EngineConfig cfg;
     Phase currentPhase = Phase::IDLE;

@@ -127,6 +127,14 @@ public:
     // leaves device memory and the pinned host buffers untouched.
     void snapshotSlots(std::vector<char>& dst);
 
+    // Which stream this context enqueues into: the hipStream_t value as an
+    // integer, for identity only (two contexts share a stream iff their ids
+    // are equal), and whether it came from the process-wide pool of
+    // EB_GPU_SHARED_STREAMS or is this context's own. Diagnostic/test hook:
+    // no device work, no I/O path calls it.
+    uint64_t streamId() const;
+    bool streamShared() const;
+
     // bind the calling thread to this context's device (hipSetDevice);
     // required when a cached context is reused by a new worker thread
     void bindThread();

@@ -1225,6 +1225,10 @@ void GpuCtx::snapshotSlots(std::vector<char>& dst)
     HIP_CHECK(hipStreamSynchronize(impl->stream));
 }
 
+uint64_t GpuCtx::streamId() const { return (uint64_t)(uintptr_t)impl->stream; }
+
+bool GpuCtx::streamShared() const { return !impl->ownStream; }
+
 void GpuCtx::copyFromHostAsync(int slot, const void* src, uint64_t len)
 {
     HIP_CHECK(hipMemcpyAsync(impl->devBufs[slot], src, len, hipMemcpyHostToDevice,

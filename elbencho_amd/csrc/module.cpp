@@ -1117,6 +1117,14 @@ PYBIND11_MODULE(_core, m)
                                        py::bytes(snap.bytes.data(), snap.bytes.size()));
              },
              py::arg("local_rank") = 0)
+        // [(stream_id, shared)] per local worker rank: which HIP stream each
+        // worker's context enqueues into; raises while a phase is running
+        .def("gpu_streams",
+             [](Engine& e) {
+                 py::list out;
+                 for (auto& s : e.gpuStreams()) out.append(py::make_tuple(s.first, s.second));
+                 return out;
+             })
         // sequence number of the current (or last) phase: 0 before the first
         // start_phase, +1 per start_phase; the per-phase seeds derive from it
         .def_property_readonly("phase_seq", [](Engine& e) { return e.phaseSeq; })

@@ -228,7 +228,7 @@ def run_write_case(core, tmp_path, capfd, monkeypatch, path_name, fill, bs, size
                         pytest.fail(f"{what}: worker {r}, block {k} (file offset {o}, slot "
                                     f"{slot_of(k, num_slots)}): "
                                     + first_diff_report(data[o:o + bs], want[o:o + bs]))
-        return
+        return eng
 
     for r, sh in enumerate(shares):
         num_slots, stride, raw = eng.gpu_slots(r)
@@ -258,6 +258,7 @@ def run_write_case(core, tmp_path, capfd, monkeypatch, path_name, fill, bs, size
                     1 if path_name.startswith("blockio") else URING_DEPTH)
             heads = {data[sh.start + k * bs:sh.start + k * bs + 64] for k in range(n)}
             assert len(heads) == n, f"{what}: worker {r}: pre-filled slots repeat"
+    return eng
 
 
 FILE_WRITE_PATHS = ["pipelined", "blockio_flock", "uring", "mmap"]
