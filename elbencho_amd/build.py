@@ -26,7 +26,7 @@ GPU_ARCH = os.environ.get("EB_GPU_ARCH", "gfx950")
 
 SOURCES = ["module.cpp", "engine.cpp", "gpu_kernels.hip"]
 HEADERS = [
-    "common.h", "crc.h", "crc64.h", "engine.h", "gpu.h", "histogram.h", "offsetgen.h",
+    "common.h", "crc.h", "crc64.h", "dataprofile.h", "engine.h", "gpu.h", "histogram.h", "offsetgen.h",
     "rand.h", "rate.h", "uring.h",
 ]
 

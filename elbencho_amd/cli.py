@@ -154,6 +154,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "between files. The block size must be a multiple of --dedupechunk. "
                         "Not with --verify, --verifymixpct, --verifydiag or unaligned random "
                         "offsets. (Default: unset)")
+    g.add_argument("--dataprofile", action="store_true",
+                   help="Profile the data that read phases (-r) move, in chunks of "
+                        "--dedupechunk: number of chunks, estimated distinct chunks "
+                        "(HyperLogLog, about 1%% error) and dedupe ratio, all-zero chunks, "
+                        "zero-byte share, order-0 entropy, and the nearest --dedupepct / "
+                        "--compresspct to replay the data set. Computed in HBM with "
+                        "--gpuids; the result does not depend on threads, block size, "
+                        "I/O depth, services or ranks. The block size must be a multiple of "
+                        "--dedupechunk. Not with S3, HDFS, netbench or --norandalign.")
 
     g = p.add_argument_group("GPU (MI355X)")
     g.add_argument("--gpuids", default="", metavar="IDS",
@@ -532,6 +541,7 @@ def args_to_config(args: argparse.Namespace) -> BenchConfig:
     cfg.compress_pct = args.compresspct
     cfg.dedupe_chunk = parse_size(args.dedupechunk)
     cfg.dedupe_verify = args.dedupeverify
+    cfg.data_profile = args.dataprofile
 
     cfg.gpu_ids = parse_gpu_ids(args.gpuids)
     cfg.gpu_per_service = args.gpuperservice

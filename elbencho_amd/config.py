@@ -119,6 +119,7 @@ class BenchConfig:
     compress_pct: int = 0          # --compresspct (percent of each chunk that is zero)
     dedupe_chunk: int = 4096       # --dedupechunk (chunk size of the two above)
     dedupe_verify: int = -1        # --dedupeverify SALT (position-keyed, checked on read)
+    data_profile: bool = False     # --dataprofile (dedupe/entropy profile of read data)
 
     # --- GPU ---
     gpu_ids: list[int] = field(default_factory=list)  # --gpuids
@@ -435,6 +436,21 @@ class BenchConfig:
             if (self.run_write or self.run_read) and self.block_size % self.dedupe_chunk:
                 raise ConfigError("--dedupeverify requires a block size that is a multiple "
                                   "of --dedupechunk")
+        if self.data_profile:
+            if not self.run_read:
+                raise ConfigError("--dataprofile requires a read phase (-r)")
+            if self.bench_mode in ("s3", "hdfs", "netbench"):
+                raise ConfigError("--dataprofile supports file, block device and "
+                                  "directory paths only")
+            if not self.rand_aligned:
+                raise ConfigError("--dataprofile cannot be used with unaligned random "
+                                  "offsets (--norandalign)")
+            c = self.dedupe_chunk
+            if not (512 <= c <= 16 << 20) or c & (c - 1):
+                raise ConfigError("--dedupechunk must be a power of two in 512..16M")
+            if self.block_size % c:
+                raise ConfigError("--dataprofile requires a block size that is a multiple "
+                                  "of --dedupechunk")
         if self.verify_mix_pct != -1:
             if not (0 <= self.verify_mix_pct <= 100):
                 raise ConfigError("verifymixpct must be in 0..100")
@@ -583,6 +599,7 @@ class BenchConfig:
             compress_pct=self.compress_pct,
             dedupe_chunk=self.dedupe_chunk,
             reduce_verify_salt=self.dedupe_verify,
+            data_profile=self.data_profile,
             rand_algo=self.rand_algo,
             gpu_ids=self.gpu_ids,
             gpu_pinned=self.gpu_pinned,

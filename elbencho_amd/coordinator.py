@@ -327,7 +327,8 @@ class Coordinator:
                                   cpu_first, cpu_last)
 
         if self.dist:
-            results = self.dist.allreduce_results(results)
+            results = self.dist.allreduce_results(
+                results, with_profile=cfg.data_profile and name == "READ")
 
         if not quiet or results.errors:
             if self.dist is None or self.dist.rank == 0:

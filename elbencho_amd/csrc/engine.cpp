@@ -911,15 +911,32 @@ void Worker::preWriteFill(int slot, uint64_t len, uint64_t fileOff)
 
 void Worker::postReadCheck(int slot, uint64_t len, uint64_t fileOff)
 {
-    if (!eng.dataVerify) return;
+    if (!eng.dataVerify && !profiling) return;
 
     if (gpu && (fileOff % 8 == 0) && (len % 16 == 0)) {
-        gpuVerifyAsync(slot, len, fileOff);
-        gpuVerifyFetch();
+        if (eng.dataVerify) gpuVerifyAsync(slot, len, fileOff);
+        profileGpuAsync(slot, len);
+        if (eng.dataVerify) gpuVerifyFetch();
         return;
     }
 
-    cpuVerify(slot, hostBufs[slot], len, fileOff);
+    if (eng.dataVerify) cpuVerify(slot, hostBufs[slot], len, fileOff);
+    profileCpu(hostBufs[slot], len);
+}
+
+// --dataprofile: the two steps that go with every verify step of a READ
+// phase. profileGpuAsync enqueues one block's profile kernel on the worker's
+// stream, behind the block's H2D copy; nothing is fetched before the phase
+// ends. profileCpu profiles a host buffer at once (no --gpuids, and the odd
+// tails that the read paths hand to cpuVerify).
+void Worker::profileGpuAsync(int slot, uint64_t len)
+{
+    if (profiling) gpu->dataProfileDevAsync(slot, len, eng.cfg.dedupeChunk);
+}
+
+void Worker::profileCpu(const char* buf, uint64_t len)
+{
+    if (profiling) dataProfileCPU(buf, len, eng.cfg.dedupeChunk, *profileAcc);
 }
 
 void Worker::setSlotFileKey(int slot, uint64_t fileKey)
@@ -1190,6 +1207,7 @@ void Worker::fileModeBlocks(bool isWrite)
     if (gpuPipelined) {
         constexpr uint64_t VERIFY_FETCH_INTERVAL = 64;
         const bool doVerify = eng.dataVerify;
+        const bool doCheck = doVerify || profiling; // per-block path, as --verify takes
         const bool lat = cfg.measureLat;
         const int nSlots = (int)hostBufs.size();
         std::vector<char> slotBusy(nSlots, 0);
@@ -1256,7 +1274,7 @@ void Worker::fileModeBlocks(bool isWrite)
             if (cfg.fsyncPerFile)
                 for (size_t i = 0; i < fg.fds.size(); i++)
                     if (fsync(fg.fds[i])) throwErrno("fsync", cfg.paths[i]);
-        } else if (!doVerify && gpuBatchSlots(cfg.blockSize) >= 2 && nSlots >= 4) {
+        } else if (!doCheck && gpuBatchSlots(cfg.blockSize) >= 2 && nSlots >= 4) {
             // batched read: fill half the ring with preads, then one ranged
             // H2D covers all of them (slots are contiguous); the other half
             // stages while this half reads. --lat: per block = its pread
@@ -1364,16 +1382,18 @@ void Worker::fileModeBlocks(bool isWrite)
 
                 gpu->copyH2DAsync(slot, ioLen);
                 if (lat) gpu->recordTimedEnd(slot);
-                if (doVerify) {
+                if (doCheck) {
                     setSlotFileKey(slot, fileIdx);
                     if ((inFileOff % 8 == 0) && (ioLen % 16 == 0)) {
-                        gpuVerifyAsync(slot, ioLen, inFileOff);
-                        if (++sinceFetch >= VERIFY_FETCH_INTERVAL) {
+                        if (doVerify) gpuVerifyAsync(slot, ioLen, inFileOff);
+                        profileGpuAsync(slot, ioLen);
+                        if (doVerify && ++sinceFetch >= VERIFY_FETCH_INTERVAL) {
                             fetchVerify();
                             sinceFetch = 0;
                         }
                     } else { // odd tail: CPU check of the host copy
-                        cpuVerify(slot, hostBufs[slot], ioLen, inFileOff);
+                        if (doVerify) cpuVerify(slot, hostBufs[slot], ioLen, inFileOff);
+                        profileCpu(hostBufs[slot], ioLen);
                     }
                 }
                 gpu->recordSlotEvent(slot);
@@ -1556,14 +1576,16 @@ void Worker::fileModeBlocksGpuMmap(bool isWrite)
             if (lat) gpu->recordTimedStart(slot);
             gpu->copyFromHostAsync(slot, bases[fileIdx] + inFileOff, ioLen);
             if (lat) gpu->recordTimedEnd(slot);
-            if (doVerify && (inFileOff % 8 == 0) && (ioLen % 16 == 0)) {
-                gpuVerifyAsync(slot, ioLen, inFileOff);
-                if (++sinceFetch >= VERIFY_FETCH_INTERVAL) {
+            if ((doVerify || profiling) && (inFileOff % 8 == 0) && (ioLen % 16 == 0)) {
+                if (doVerify) gpuVerifyAsync(slot, ioLen, inFileOff);
+                profileGpuAsync(slot, ioLen);
+                if (doVerify && ++sinceFetch >= VERIFY_FETCH_INTERVAL) {
                     fetchVerify();
                     sinceFetch = 0;
                 }
-            } else if (doVerify) { // odd tail: check the mapped pages directly
-                cpuVerify(slot, bases[fileIdx] + inFileOff, ioLen, inFileOff);
+            } else if (doVerify || profiling) { // odd tail: check the mapped pages directly
+                if (doVerify) cpuVerify(slot, bases[fileIdx] + inFileOff, ioLen, inFileOff);
+                profileCpu(bases[fileIdx] + inFileOff, ioLen);
             }
         }
 
@@ -1668,7 +1690,7 @@ void Worker::fileModeBlocksUring(bool isWrite)
     // half-ring batching (5.1M vs 3.4M IOPS warm), so batching here is
     // opt-in (EB_GPU_URING_BATCH=1) — unlike the sync path where it wins
     const int gpuBatch = gpu ? gpuBatchSlots(bs) : 1;
-    const bool batchedRead = gpu && !isWrite && !eng.dataVerify &&
+    const bool batchedRead = gpu && !isWrite && !eng.dataVerify && !profiling &&
                              gpuBatch >= 2 && depth >= 4 &&
                              getenv("EB_GPU_URING_BATCH");
     if (getenv("EB_DEBUG_PATH"))
@@ -1855,7 +1877,7 @@ void Worker::fileModeBlocksUring(bool isWrite)
             if (!wasWrite) {
                 if (gpu) {
                     gpu->copyH2DAsync(slot, st.len);
-                    if (eng.dataVerify && !isWrite) {
+                    if ((eng.dataVerify || profiling) && !isWrite) {
                         gpu->syncStream();
                         postReadCheck(slot, st.len, st.inFileOff);
                     } else { // pipelined: wait only when the slot is reused
@@ -2085,7 +2107,7 @@ void Worker::uringFileBlocks(FileUring& u, int fd, const std::string& path,
                 const bool check = !phaseIsWrite || checkMixReads;
                 if (gpu) {
                     gpu->copyH2DAsync(slot, st.len);
-                    if (eng.dataVerify && check) {
+                    if ((eng.dataVerify && check) || profiling) {
                         gpu->syncStream();
                         postReadCheck(slot, st.len, st.off);
                     } else { // pipelined: wait only when the slot is reused
@@ -2127,7 +2149,7 @@ bool Worker::dirModeSmallFileUring(bool isWrite)
     const uint64_t numDirs = haveSubdirs ? cfg.numDirs : 1;
     const int dirRank = cfg.dirSharing ? 0 : globalRank;
     const int depth = std::min<int>(cfg.ioDepth, (int)hostBufs.size());
-    const bool doVerify = eng.dataVerify;
+    const bool doVerify = eng.dataVerify || profiling; // per-file check after the copy
 
     int openFlags = isWrite ? (O_CREAT | O_WRONLY) : O_RDONLY;
     if (cfg.directIO) openFlags |= O_DIRECT;
@@ -3126,6 +3148,15 @@ void Worker::threadMain()
                 allocBuffers();
             if (eng.reduceVerify) slotReduceSeed.resize(hostBufs.size());
 
+            // --dataprofile: READ phases only (not the reads of an rwmix
+            // write phase); accumulators start empty in every phase
+            profiling = eng.dataProfile && eng.currentPhase == Phase::READ;
+            profileResult.reset();
+            if (profiling) {
+                profileAcc = std::make_unique<DataProfileAcc>();
+                if (gpu) gpu->dataProfileReset();
+            }
+
             rateLimiter.init((eng.currentPhase == Phase::WRITE && !isDedicatedReader)
                                  ? eng.cfg.limitWriteBps
                                  : eng.cfg.limitReadBps);
@@ -3138,6 +3169,11 @@ void Worker::threadMain()
                 reduceNextChunk = 0;
                 runPhase();
             } while (loopingPhase && !eng.interruptFlag.load(std::memory_order_relaxed));
+
+            if (profiling) { // the one fetch of the phase; an error reports none
+                if (gpu) gpu->dataProfileFetch(*profileAcc);
+                profileResult = std::move(profileAcc);
+            }
         } catch (const InterruptedError&) {
             error = "interrupted";
             hadError = true;
@@ -3209,6 +3245,19 @@ Engine::Engine(EngineConfig cfgIn) : cfg(std::move(cfgIn))
         reduceVerify = true;
     }
     dataVerify = cfg.verifySalt >= 0 || reduceVerify;
+
+    if (cfg.dataProfile) {
+        if (!dataProfileChunkOk(cfg.dedupeChunk))
+            throw std::invalid_argument(
+                "data_profile requires a dedupe_chunk that is a power of two in 512..16M");
+        if (cfg.random && !cfg.randAligned)
+            throw std::invalid_argument(
+                "data_profile cannot be used with unaligned random offsets");
+        if (!cfg.blockSize || cfg.blockSize % cfg.dedupeChunk)
+            throw std::invalid_argument(
+                "data_profile requires a block size that is a multiple of dedupe_chunk");
+        dataProfile = true;
+    }
 }
 
 Engine::~Engine()
@@ -3453,6 +3502,7 @@ std::vector<WorkerResult> Engine::finishPhase()
         r.ioLatReadMixVec = w->ioLatReadMix.toVec();
         r.entryLatReadMixVec = w->entryLatReadMix.toVec();
         r.error = w->error;
+        if (w->error.empty()) r.profile = w->profileResult;
         results.push_back(std::move(r));
     }
 

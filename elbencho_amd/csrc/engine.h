@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "dataprofile.h"
 #include "gpu.h"
 #include "histogram.h"
 #include "offsetgen.h"
@@ -72,6 +73,9 @@ struct EngineConfig {
     // --dedupeverify SALT: reduce pattern keyed by (SALT, file, file offset)
     // and checked on read; < 0 off. Needs dedupePct / compressPct > 0.
     int64_t reduceVerifySalt = -1;
+    // --dataprofile: READ phases profile what they read (dataprofile.h), in
+    // chunks of dedupeChunk bytes
+    bool dataProfile = false;
     std::string blockVarAlgo = "fast";
     std::string randAlgo = "fast";
 
@@ -151,6 +155,9 @@ struct WorkerResult {
     std::vector<uint64_t> ioLatReadMixVec;
     std::vector<uint64_t> entryLatReadMixVec;
     std::string error;
+    // --dataprofile: what this worker read in a READ phase; null when the
+    // option is off, in other phases and when the worker ended in an error
+    std::shared_ptr<DataProfileAcc> profile;
 };
 
 class Engine;
@@ -189,6 +196,10 @@ public:
     // this (persistent) worker. Called from the engine thread while the
     // worker is parked at the phase gate.
     void resetPhaseStats();
+
+    // --dataprofile: the finished phase's profile (set by the worker thread
+    // before it reports done, read by Engine::finishPhase)
+    std::shared_ptr<DataProfileAcc> profileResult;
 
     // this worker's GPU context (nullptr without --gpuids or before its first
     // data phase); only for use while the worker is parked at the phase gate
@@ -267,6 +278,9 @@ private:
     // --dedupeverify: the seeds of the file that the slot's block belongs to
     void setSlotFileKey(int slot, uint64_t fileKey);
     void setAllSlotFileKeys(uint64_t fileKey);
+    // --dataprofile steps of the read paths; no-ops unless `profiling`
+    void profileGpuAsync(int slot, uint64_t len);
+    void profileCpu(const char* buf, uint64_t len);
     ssize_t blockIO(bool isWrite, int fd, int slot, uint64_t len, uint64_t fileOff,
                     char* mmapBase = nullptr, const std::string* path = nullptr);
     void verifyDirectReadback(int fd, int slot, uint64_t len, uint64_t fileOff);
@@ -293,6 +307,10 @@ private:
     // --dedupeverify: per I/O slot, the seeds of the file whose block the slot
     // holds (several files are in flight per worker on the io_uring paths)
     std::vector<ReduceSeeds> slotReduceSeed;
+    // --dataprofile: on in this phase; host accumulator (CPU-profiled blocks,
+    // and the device state after the phase's one fetch)
+    bool profiling = false;
+    std::unique_ptr<DataProfileAcc> profileAcc;
     RateLimiter rateLimiter;
 };
 
@@ -398,6 +416,8 @@ public:
     // by --verify or by --dedupeverify
     bool reduceVerify = false;
     bool dataVerify = false;
+    // --dataprofile on (fixed at construction)
+    bool dataProfile = false;
 
     // GPU contexts cached across phases (hipMalloc + pinned allocs are
     // expensive; reusing them keeps phase setup off the measured path)

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "crc.h"
+#include "dataprofile.h"
 
 namespace eb {
 
@@ -85,6 +86,12 @@ double gpuReduceVerifyBenchGBs(uint64_t len, int iters, int dev, uint64_t chunkB
 
 // gpuVerifyBenchGBs for ebVerifyDiagKernel: same buffer, same clean data.
 double gpuVerifyDiagBenchGBs(uint64_t len, int iters, int dev);
+
+// Micro-bench of ebDataProfileKernel (GB/s) on one len-byte buffer cut into
+// chunkBytes chunks, timed as gpuMixBenchGBs times its verify. kind selects the
+// content: 0 random words, 1 zero-heavy (the second half of every 4 KiB is
+// zero, as --compresspct 50 writes it), 2 all zero.
+double gpuDataProfileBenchGBs(uint64_t len, int iters, int dev, uint64_t chunkBytes, int kind);
 
 // Geometry of the device CRC kernel: bytes per tile (one raw partial CRC
 // each) and bytes covered by one wave within a tile. Tests key their sizes
@@ -293,10 +300,26 @@ public:
     uint64_t crc64Fetch(uint64_t totalLen, uint64_t tileCount);
     uint64_t crc64Dev(int slot, uint64_t len);
 
+    // --- --dataprofile (ebDataProfileKernel; contract at dataprofile.h) ---
+    // The accumulators (sketch registers, byte histogram, counters) live in
+    // device memory of this context's own, allocated on the first call of any
+    // of the three; contexts that share a stream do not share them.
+    // dataProfileReset zeroes them with one async memset on the stream.
+    // dataProfileDevAsync adds the profile of the slot's first len bytes, cut
+    // into chunkBytes chunks (dataProfileChunkOk, else std::invalid_argument;
+    // any len up to the slot size, len == 0 launches nothing): it reads the
+    // slot and writes nothing but the accumulators. dataProfileFetch
+    // synchronizes the stream and merges the device state into acc; it does
+    // not reset.
+    void dataProfileReset();
+    void dataProfileDevAsync(int slot, uint64_t len, uint64_t chunkBytes);
+    void dataProfileFetch(DataProfileAcc& acc);
+
 private:
     struct Impl;
     Impl* impl;
     unsigned long long* diagRecordDev(); // device record, allocated on first use
+    void dataProfileAlloc();             // device accumulators, on first use
     int devId;
     uint64_t slotSize;
     int slots;

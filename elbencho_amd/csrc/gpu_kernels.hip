@@ -977,6 +977,162 @@ __global__ __launch_bounds__(256) void ebCrc64TilesKernel(const ulonglong2* __re
 }
 
 // ---------------------------------------------------------------------------
+// --dataprofile (contract: dataprofile.h)
+// ---------------------------------------------------------------------------
+
+// The bytes of one u64 word (the first nBytes are real, the rest masked to 0)
+// for the byte histogram. Zero bytes are counted in a register: zero-heavy
+// data is the expected input, and 64 lanes adding to one LDS address
+// serialise. The others go to the wave's private LDS histogram h.
+__device__ __forceinline__ void d_profileWord(uint64_t w, uint32_t nBytes,
+                                              uint32_t* __restrict__ h,
+                                              unsigned long long& zeros)
+{
+    if (w == 0) {
+        zeros += nBytes;
+        return;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) {
+        const uint32_t b = (uint32_t)(w >> (8 * j)) & 0xFFu;
+        if (j < nBytes) {
+            if (b)
+                atomicAdd(&h[b], 1u);
+            else
+                zeros++;
+        }
+    }
+}
+
+// One team owns one chunk at a time and strides over the chunks: a wave
+// (WG = false, chunks below DP_WG_CHUNK_BYTES) or the whole workgroup (WG =
+// true: larger chunks would leave one wave alone with too many bytes). Lanes
+// take 16 B elements of the chunk, four loads in flight each; an element that
+// the chunk's end cuts is masked by byte, so nothing at or past len is
+// counted (the load itself may cover up to 15 bytes past len: the caller
+// keeps those inside the allocation). The team sum-reduces S and OR-reduces
+// "any non-zero byte" (wave64 shuffles, plus LDS between the waves of a
+// workgroup team); one lane finishes the fingerprint and does the one
+// atomicMax on its sketch register. Counters are summed per workgroup, the
+// byte histogram per wave in LDS (4 KiB per workgroup); at the end one global
+// 64-bit atomic per non-empty bin and per counter. The kernel reads buf and
+// writes regs, hist and counters only.
+constexpr uint64_t DP_WG_CHUNK_BYTES = 16384;
+constexpr int DP_LOADS_IN_FLIGHT = 4;
+
+template <bool WG>
+__global__ __launch_bounds__(256) void ebDataProfileKernel(
+    const ulonglong2* __restrict__ buf, uint64_t len, uint32_t chunkShift,
+    unsigned int* __restrict__ regs,          // [DP_HLL_M]
+    unsigned long long* __restrict__ hist,    // [256]
+    unsigned long long* __restrict__ counters) // chunks, bytes, zeroChunks
+{
+    __shared__ uint32_t sHist[4][256];
+    __shared__ unsigned long long sPart[4][2]; // workgroup team: per-wave S, any
+    __shared__ unsigned long long sCnt[4][4];  // per wave: the counters, zero bytes
+
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = threadIdx.x >> 6;
+    for (uint32_t i = threadIdx.x; i < 4 * 256; i += 256) (&sHist[0][0])[i] = 0;
+    __syncthreads();
+
+    constexpr uint32_t TEAM = WG ? 256 : 64;
+    const uint64_t chunkBytes = 1ULL << chunkShift;
+    const uint64_t nChunks = (len + chunkBytes - 1) >> chunkShift;
+    const uint64_t team = WG ? (uint64_t)blockIdx.x : (uint64_t)blockIdx.x * 4 + wave;
+    const uint64_t nTeams = WG ? (uint64_t)gridDim.x : (uint64_t)gridDim.x * 4;
+    const uint32_t teamLane = WG ? threadIdx.x : lane;
+    const bool finisher = teamLane == 0;
+    uint32_t* __restrict__ h = sHist[wave];
+
+    unsigned long long zeros = 0; // per lane
+    unsigned long long myChunks = 0, myBytes = 0, myZeroChunks = 0; // finisher only
+
+    for (uint64_t k = team; k < nChunks; k += nTeams) {
+        const uint64_t start = k << chunkShift;
+        const uint64_t n = (len - start < chunkBytes) ? len - start : chunkBytes;
+        const uint64_t nv = (n + 15) / 16; // 16 B elements, the last one maybe cut
+        const ulonglong2* __restrict__ src = buf + (start >> 4);
+
+        unsigned long long S = 0, any = 0;
+        for (uint64_t base = 0; base < nv; base += (uint64_t)TEAM * DP_LOADS_IN_FLIGHT) {
+            ulonglong2 val[DP_LOADS_IN_FLIGHT];
+#pragma unroll
+            for (int u = 0; u < DP_LOADS_IN_FLIGHT; u++) {
+                const uint64_t v = base + (uint64_t)u * TEAM + teamLane;
+                val[u].x = 0;
+                val[u].y = 0;
+                if (v < nv) val[u] = src[v]; // 16 B/lane coalesced read
+            }
+#pragma unroll
+            for (int u = 0; u < DP_LOADS_IN_FLIGHT; u++) {
+                const uint64_t v = base + (uint64_t)u * TEAM + teamLane;
+                if (v >= nv) continue;
+                const uint64_t rem = n - v * 16; // real bytes from this element on, >= 1
+                uint64_t x = val[u].x, y = val[u].y;
+                uint32_t nx = 8, ny = 8;
+                if (rem < 16) { // the chunk ends inside this element
+                    nx = rem < 8 ? (uint32_t)rem : 8;
+                    ny = rem > 8 ? (uint32_t)rem - 8 : 0;
+                    if (nx < 8) x &= (1ULL << (8 * nx)) - 1;
+                    y = ny ? y & ((1ULL << (8 * ny)) - 1) : 0; // ny <= 7 here
+                }
+                S += dpWordTerm(x, 2 * v);
+                if (ny) S += dpWordTerm(y, 2 * v + 1);
+                any |= x | y;
+                d_profileWord(x, nx, h, zeros);
+                d_profileWord(y, ny, h, zeros);
+            }
+        }
+
+#pragma unroll
+        for (int delta = 32; delta > 0; delta >>= 1) {
+            S += __shfl_down(S, delta, 64);
+            any |= __shfl_down(any, delta, 64);
+        }
+        if (WG) { // k depends on blockIdx alone: every thread gets here
+            if (lane == 0) {
+                sPart[wave][0] = S;
+                sPart[wave][1] = any;
+            }
+            __syncthreads();
+            if (finisher) {
+                S = sPart[0][0] + sPart[1][0] + sPart[2][0] + sPart[3][0];
+                any = sPart[0][1] | sPart[1][1] | sPart[2][1] | sPart[3][1];
+            }
+            __syncthreads(); // sPart is rewritten for the next chunk
+        }
+        if (finisher) {
+            const uint64_t fp = dpFingerprint(S, n);
+            atomicMax(&regs[dpRegIndex(fp)], dpRho(fp));
+            myChunks++;
+            myBytes += n;
+            if (!any) myZeroChunks++;
+        }
+    }
+
+#pragma unroll
+    for (int delta = 32; delta > 0; delta >>= 1) zeros += __shfl_down(zeros, delta, 64);
+    if (lane == 0) {
+        sCnt[wave][0] = myChunks;
+        sCnt[wave][1] = myBytes;
+        sCnt[wave][2] = myZeroChunks;
+        sCnt[wave][3] = zeros;
+    }
+    __syncthreads();
+
+    const uint32_t t = threadIdx.x; // owns bin t; threads 0..2 a counter too
+    unsigned long long bin = (unsigned long long)sHist[0][t] + sHist[1][t] + sHist[2][t] +
+                             sHist[3][t];
+    if (t == 0) bin += sCnt[0][3] + sCnt[1][3] + sCnt[2][3] + sCnt[3][3];
+    if (bin) atomicAdd(&hist[t], bin);
+    if (t < 3) {
+        const unsigned long long c = sCnt[0][t] + sCnt[1][t] + sCnt[2][t] + sCnt[3][t];
+        if (c) atomicAdd(&counters[t], c);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host wrappers
 // ---------------------------------------------------------------------------
 
@@ -1118,7 +1274,16 @@ struct GpuCtx::Impl {
     uint64_t* crc64PartHost = nullptr;           // pinned mirror
     uint64_t crc64PartCap = 0;                   // in partials
     std::vector<CrcCall> crc64Pending;           // enqueued since the last fetch
+
+    // --dataprofile accumulators, allocated by the first dataProfile* call:
+    // u32 regs[DP_HLL_M], then u64 hist[256], then u64 counters[4] (3 used)
+    char* dpDev = nullptr;
+    char* dpHost = nullptr; // pinned mirror
 };
+
+constexpr size_t DP_REGS_BYTES = DP_HLL_M * sizeof(unsigned int);
+constexpr size_t DP_HIST_BYTES = 256 * sizeof(unsigned long long);
+constexpr size_t DP_DEV_BYTES = DP_REGS_BYTES + DP_HIST_BYTES + 4 * sizeof(unsigned long long);
 
 GpuCtx::GpuCtx(int deviceId, int numSlots, uint64_t bufSize, bool pinnedHostBufs)
     : impl(new Impl), devId(deviceId), slotSize(bufSize), slots(numSlots)
@@ -1206,6 +1371,8 @@ GpuCtx::~GpuCtx()
     if (impl->crc64TabDev) (void)hipFree(impl->crc64TabDev);
     if (impl->crc64PartDev) (void)hipFree(impl->crc64PartDev);
     if (impl->crc64PartHost) (void)hipHostFree(impl->crc64PartHost);
+    if (impl->dpDev) (void)hipFree(impl->dpDev);
+    if (impl->dpHost) (void)hipHostFree(impl->dpHost);
     if (impl->stream && impl->ownStream) (void)hipStreamDestroy(impl->stream);
     delete impl;
 }
@@ -1676,6 +1843,83 @@ GpuVerifyResult GpuCtx::verifyReduceDev(int slot, uint64_t len, uint64_t fileOff
 uint64_t gpuCrcTileBytes() { return CRC_TILE_BYTES; }
 uint64_t gpuCrcWaveBytes() { return CRC_WAVE_BYTES; }
 
+void GpuCtx::dataProfileAlloc()
+{
+    if (impl->dpDev) return;
+    HIP_CHECK(hipMalloc(&impl->dpDev, DP_DEV_BYTES));
+    HIP_CHECK(hipHostMalloc(&impl->dpHost, DP_DEV_BYTES, hipHostMallocDefault));
+    HIP_CHECK(hipMemsetAsync(impl->dpDev, 0, DP_DEV_BYTES, impl->stream));
+}
+
+void GpuCtx::dataProfileReset()
+{
+    const bool fresh = !impl->dpDev;
+    dataProfileAlloc();
+    if (!fresh) HIP_CHECK(hipMemsetAsync(impl->dpDev, 0, DP_DEV_BYTES, impl->stream));
+}
+
+static dim3 gridForProfile(uint64_t nChunks, bool wgTeam)
+{
+    // one team per chunk until the grid fills the chip several times over;
+    // every workgroup ends with up to 259 global atomics, so no more than that
+    uint64_t blocks = wgTeam ? nChunks : (nChunks + 3) / 4;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks == 0) blocks = 1;
+    return dim3((uint32_t)blocks);
+}
+
+static void launchDataProfile(hipStream_t stream, const void* buf, uint64_t len,
+                              uint64_t chunkBytes, char* acc)
+{
+    const uint32_t chunkShift = (uint32_t)__builtin_ctzll(chunkBytes);
+    const uint64_t nChunks = (len + chunkBytes - 1) / chunkBytes;
+    const bool wgTeam = chunkBytes >= DP_WG_CHUNK_BYTES;
+    unsigned int* regs = (unsigned int*)acc;
+    unsigned long long* hist = (unsigned long long*)(acc + DP_REGS_BYTES);
+    unsigned long long* counters = hist + 256;
+    if (wgTeam)
+        hipLaunchKernelGGL(ebDataProfileKernel<true>, gridForProfile(nChunks, true), dim3(256),
+                           0, stream, (const ulonglong2*)buf, len, chunkShift, regs, hist,
+                           counters);
+    else
+        hipLaunchKernelGGL(ebDataProfileKernel<false>, gridForProfile(nChunks, false),
+                           dim3(256), 0, stream, (const ulonglong2*)buf, len, chunkShift, regs,
+                           hist, counters);
+    HIP_CHECK(hipGetLastError());
+}
+
+void GpuCtx::dataProfileDevAsync(int slot, uint64_t len, uint64_t chunkBytes)
+{
+    if (!dataProfileChunkOk(chunkBytes))
+        throw std::invalid_argument("dataProfileDev: chunk must be a power of two in 512..16M");
+    if (slot < 0 || slot >= slots)
+        throw std::invalid_argument("dataProfileDev: no such slot");
+    // a cut last 16 B element is loaded whole: it must end inside the slot
+    if (len > impl->slotStride)
+        throw std::invalid_argument("dataProfileDev: len " + std::to_string(len) +
+                                    " exceeds the slot size");
+    dataProfileAlloc();
+    if (!len) return;
+    launchDataProfile(impl->stream, impl->devBufs[slot], len, chunkBytes, impl->dpDev);
+}
+
+void GpuCtx::dataProfileFetch(DataProfileAcc& acc)
+{
+    if (!impl->dpDev) return; // nothing was ever enqueued
+    HIP_CHECK(hipMemcpyAsync(impl->dpHost, impl->dpDev, DP_DEV_BYTES, hipMemcpyDeviceToHost,
+                             impl->stream));
+    HIP_CHECK(hipStreamSynchronize(impl->stream));
+    const unsigned int* regs = (const unsigned int*)impl->dpHost;
+    const unsigned long long* hist = (const unsigned long long*)(impl->dpHost + DP_REGS_BYTES);
+    const unsigned long long* counters = hist + 256;
+    for (uint32_t i = 0; i < DP_HLL_M; i++)
+        acc.regs[i] = (uint8_t)std::max<unsigned int>(acc.regs[i], regs[i]);
+    for (int i = 0; i < 256; i++) acc.hist[i] += hist[i];
+    acc.chunks += counters[0];
+    acc.bytes += counters[1];
+    acc.zeroChunks += counters[2];
+}
+
 void GpuCtx::crcDevAsync(int slot, uint64_t len, CrcAlgo algo, uint64_t partialBase)
 {
     requireAligned("crcDevAsync", len, 16);
@@ -2058,6 +2302,55 @@ double gpuReduceVerifyBenchGBs(uint64_t len, int iters, int dev, uint64_t chunkB
     (void)hipFree(out);
 
     if (bad) throw std::runtime_error("gpuReduceVerifyBenchGBs: the clean buffer did not verify");
+    return (double)len * iters / (ms / 1000.0) / 1e9;
+}
+
+double gpuDataProfileBenchGBs(uint64_t len, int iters, int dev, uint64_t chunkBytes, int kind)
+{
+    requireAligned("gpuDataProfileBenchGBs", len, 16);
+    if (!dataProfileChunkOk(chunkBytes))
+        throw std::invalid_argument(
+            "gpuDataProfileBenchGBs: chunk must be a power of two in 512..16M");
+    if (kind < 0 || kind > 2) throw std::invalid_argument("gpuDataProfileBenchGBs: bad kind");
+    if (!len || iters < 1) throw std::invalid_argument("gpuDataProfileBenchGBs: nothing to run");
+    HIP_CHECK(hipSetDevice(dev));
+    const uint64_t nVec2 = len / 16;
+    ulonglong2* buf = nullptr;
+    char* acc = nullptr;
+    HIP_CHECK(hipMalloc(&buf, len));
+    HIP_CHECK(hipMalloc(&acc, DP_DEV_BYTES));
+    HIP_CHECK(hipMemset(acc, 0, DP_DEV_BYTES));
+
+    hipStream_t s;
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+
+    // the data the kernel reads: 4 KiB pattern chunks, all unique, of which
+    // everything (kind 0), the first half (1) or nothing (2) is random
+    hipLaunchKernelGGL(ebFillReduceKernel, gridForBytes(nVec2), dim3(256), 0, s, buf, nVec2,
+                       (uint64_t)0, 0u, 8u, (uint64_t)(kind == 0 ? 256 : kind == 1 ? 128 : 0),
+                       0u, (uint64_t)256, (uint64_t)42, (uint64_t)43);
+    auto launch = [&] { launchDataProfile(s, buf, len, chunkBytes, acc); };
+
+    launch(); // warmup
+    launch();
+    HIP_CHECK(hipStreamSynchronize(s));
+
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    HIP_CHECK(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; i++) launch();
+    HIP_CHECK(hipEventRecord(e1, s));
+    HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(buf);
+    (void)hipFree(acc);
+
     return (double)len * iters / (ms / 1000.0) / 1e9;
 }
 

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <optional>
 #include <unistd.h>
@@ -66,6 +67,27 @@ py::dict diagToDict(const GpuVerifyDiag& r)
     d["delta_max"] = r.deltaMax;
     d["flip_or"] = r.flipOr;
     return d;
+}
+
+// a DataProfileAcc as it crosses the binding
+py::dict profileToDict(const DataProfileAcc& a)
+{
+    py::dict d;
+    d["chunks"] = a.chunks;
+    d["bytes"] = a.bytes;
+    d["zero_chunks"] = a.zeroChunks;
+    py::list hist;
+    for (uint64_t v : a.hist) hist.append(v);
+    d["hist"] = hist;
+    d["regs"] = py::bytes((const char*)a.regs, DP_HLL_M);
+    return d;
+}
+
+void requireProfileChunk(const char* what, uint64_t chunk)
+{
+    if (!dataProfileChunkOk(chunk))
+        throw std::invalid_argument(std::string(what) +
+                                    ": chunk must be a power of two in 512..16M");
 }
 
 EngineConfig configFromDict(const py::dict& d)
@@ -149,6 +171,7 @@ EngineConfig configFromDict(const py::dict& d)
     c.compressPct = (int)getI("compress_pct", 0);
     c.dedupeChunk = getU64("dedupe_chunk", 4096);
     c.reduceVerifySalt = getI("reduce_verify_salt", -1);
+    c.dataProfile = getB("data_profile", false);
     c.randAlgo = getS("rand_algo", "balanced_single");
     if (d.contains("gpu_ids")) c.gpuIDs = d["gpu_ids"].cast<std::vector<int>>();
     c.gpuPinnedHostBufs = getB("gpu_pinned", true);
@@ -187,6 +210,7 @@ py::dict resultToDict(const WorkerResult& r)
     d["io_lat_rm"] = r.ioLatReadMixVec;
     d["entry_lat_rm"] = r.entryLatReadMixVec;
     d["error"] = r.error;
+    if (r.profile) d["data_profile"] = profileToDict(*r.profile);
     return d;
 }
 
@@ -314,6 +338,15 @@ PYBIND11_MODULE(_core, m)
           py::arg("file"));
 
     // --verifydiag on the CPU; block_size 0 selects the plain pattern
+    // --dataprofile: the CPU twin over one block
+    m.def("data_profile", [](py::bytes data, uint64_t chunk) {
+        requireProfileChunk("data_profile", chunk);
+        std::string buf = data;
+        auto acc = std::make_unique<DataProfileAcc>();
+        dataProfileCPU(buf.data(), buf.size(), chunk, *acc);
+        return profileToDict(*acc);
+    }, py::arg("data"), py::arg("chunk") = 4096);
+
     m.def("verify_diag", [](py::bytes data, uint64_t fileOff, uint64_t salt,
                             uint64_t blockSize, uint64_t mixLen) {
         std::string buf = data;
@@ -640,6 +673,84 @@ PYBIND11_MODULE(_core, m)
     }, py::arg("items"), py::arg("salt"), py::arg("block_size"), py::arg("mix_len"),
        py::arg("plain_items") = std::vector<std::pair<py::bytes, uint64_t>>{},
        py::arg("dev") = 0);
+
+    // --- --dataprofile kernel ---
+
+    // One block through ebDataProfileKernel. The whole slot is filled with
+    // 0xA5 before data is copied in, on the host and on the device, so a
+    // kernel that counts or hashes anything at or past len shows up.
+    m.def("gpu_data_profile", [](py::bytes data, uint64_t chunk, int dev) {
+        requireProfileChunk("gpu_data_profile", chunk);
+        std::string buf = data;
+        GpuCtx ctx(dev, 1, std::max<uint64_t>(buf.size(), 16), true);
+        std::memset(ctx.hostBuf(0), 0xA5, ctx.slotStride());
+        std::memcpy(ctx.hostBuf(0), buf.data(), buf.size());
+        ctx.copyH2DAsync(0, ctx.slotStride());
+        ctx.dataProfileReset();
+        ctx.dataProfileDevAsync(0, buf.size(), chunk);
+        auto acc = std::make_unique<DataProfileAcc>();
+        ctx.dataProfileFetch(*acc);
+        return profileToDict(*acc);
+    }, py::arg("data"), py::arg("chunk") = 4096, py::arg("dev") = 0);
+
+    // Several blocks with no fetch in between. contexts = 1: all of them into
+    // one context, one slot each. contexts = 2: two contexts on one stream of
+    // the shared pool, block i into context i % 2. Returns one profile per
+    // context.
+    m.def("gpu_data_profile_batch", [](const std::vector<py::bytes>& items, uint64_t chunk,
+                                       int dev, int contexts) {
+        requireProfileChunk("gpu_data_profile_batch", chunk);
+        if (items.empty()) throw std::invalid_argument("gpu_data_profile_batch: no items");
+        if (contexts != 1 && contexts != 2)
+            throw std::invalid_argument("gpu_data_profile_batch: contexts must be 1 or 2");
+        std::vector<std::string> bufs;
+        uint64_t maxLen = 16;
+        for (const auto& it : items) {
+            bufs.emplace_back(it);
+            maxLen = std::max<uint64_t>(maxLen, bufs.back().size());
+        }
+        std::vector<std::unique_ptr<GpuCtx>> ctxs;
+        ctxs.push_back(std::make_unique<GpuCtx>(dev, (int)bufs.size(), maxLen, true));
+        // the pool hands its streams out in turn: make contexts until one gets
+        // the first one's stream again (at most 64 streams per device)
+        for (int tries = 0; contexts == 2 && ctxs.size() < 2; tries++) {
+            if (!ctxs[0]->streamShared() || tries > 64)
+                throw std::runtime_error("gpu_data_profile_batch: no shared stream pool "
+                                         "(EB_GPU_SHARED_STREAMS=0?)");
+            auto c = std::make_unique<GpuCtx>(dev, (int)bufs.size(), maxLen, true);
+            if (c->streamId() == ctxs[0]->streamId()) ctxs.push_back(std::move(c));
+        }
+        for (auto& c : ctxs) c->dataProfileReset();
+        for (size_t i = 0; i < bufs.size(); i++) {
+            GpuCtx& c = *ctxs[i % contexts];
+            std::memset(c.hostBuf((int)i), 0xA5, c.slotStride());
+            std::memcpy(c.hostBuf((int)i), bufs[i].data(), bufs[i].size());
+            c.copyH2DAsync((int)i, c.slotStride());
+            c.dataProfileDevAsync((int)i, bufs[i].size(), chunk);
+        }
+        py::list out;
+        for (auto& c : ctxs) {
+            auto acc = std::make_unique<DataProfileAcc>();
+            c->dataProfileFetch(*acc);
+            out.append(profileToDict(*acc));
+        }
+        return out;
+    }, py::arg("items"), py::arg("chunk") = 4096, py::arg("dev") = 0,
+       py::arg("contexts") = 1);
+
+    // GB/s of ebDataProfileKernel on one len-byte buffer
+    m.def("gpu_data_profile_bench_gbs",
+          [](uint64_t len, int iters, int dev, const std::string& kind, uint64_t chunk) {
+              const int k = kind == "random" ? 0 : kind == "zero-heavy" ? 1
+                            : kind == "all-zero" ? 2 : -1;
+              if (k < 0)
+                  throw std::invalid_argument("gpu_data_profile_bench_gbs: kind must be "
+                                              "random, zero-heavy or all-zero");
+              py::gil_scoped_release rel;
+              return gpuDataProfileBenchGBs(len, iters, dev, chunk, k);
+          },
+          py::arg("len"), py::arg("iters") = 50, py::arg("dev") = 0,
+          py::arg("kind") = "random", py::arg("chunk") = 4096);
 
     // --- --verifydiag kernels; block_size 0 selects the plain kernel ---
 

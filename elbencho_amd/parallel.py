@@ -24,6 +24,7 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
+from elbencho_amd.dataprofile import HLL_M, DataProfile
 from elbencho_amd.stats import PhaseResults
 
 
@@ -152,8 +153,13 @@ class PhaseSync:
             dist.barrier()
 
     # ------------------------------------------------------------------
-    def allreduce_results(self, r: PhaseResults) -> PhaseResults:
+    def allreduce_results(self, r: PhaseResults, with_profile: bool = False) -> PhaseResults:
         """Aggregate a per-rank PhaseResults into the whole-job result.
+
+        with_profile (--dataprofile READ phases; the same on every rank): the
+        profile's counters and byte histogram ride the SUM tensor and its
+        sketch registers the MAX tensor. Otherwise the tensors keep their
+        plain length.
 
         One SUM all-reduce carries counters + both histograms' buckets; one
         MIN and one MAX carry the time/min/max fields — 3 small collectives
@@ -170,6 +176,11 @@ class PhaseSync:
         ]
         sum_vals += r.io_lat.vec[4:]
         sum_vals += r.entry_lat.vec[4:]
+        if with_profile:  # a rank without a profile (worker error) adds an empty one
+            prof = r.data_profile or DataProfile()
+            sum_vals += [1 if r.data_profile else 0, prof.chunks, prof.bytes,
+                         prof.zero_chunks]
+            sum_vals += prof.hist
         t_sum = torch.tensor(sum_vals, dtype=torch.float64, device=self.device)
         dist.all_reduce(t_sum, op=dist.ReduceOp.SUM)
 
@@ -181,9 +192,10 @@ class PhaseSync:
         dist.all_reduce(t_min, op=dist.ReduceOp.MIN)
 
         # --- MAX: last-finish elapsed + histogram maxes ---
-        t_max = torch.tensor(
-            [r.last_finish_usec, r.io_lat.vec[3], r.entry_lat.vec[3]],
-            dtype=torch.float64, device=self.device)
+        max_vals = [r.last_finish_usec, r.io_lat.vec[3], r.entry_lat.vec[3]]
+        if with_profile:
+            max_vals += list(prof.regs)
+        t_max = torch.tensor(max_vals, dtype=torch.float64, device=self.device)
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
 
         s = [int(x) for x in t_sum.tolist()]
@@ -203,6 +215,12 @@ class PhaseSync:
         out.entry_lat.vec = [s[8], s[9], mn[2], mx[2]] + s[10 + nb:10 + 2 * nb]
         out.errors = list(r.errors)
         out.worker_elapsed_usec = list(r.worker_elapsed_usec)
+        if with_profile:
+            p0 = 10 + 2 * nb
+            if s[p0] == self.world_size:  # every rank finished its part
+                out.data_profile = DataProfile(
+                    chunks=s[p0 + 1], bytes=s[p0 + 2], zero_chunks=s[p0 + 3],
+                    hist=s[p0 + 4:p0 + 4 + 256], regs=bytes(mx[3:3 + HLL_M]))
         return out
 
     # ------------------------------------------------------------------

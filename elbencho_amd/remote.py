@@ -20,6 +20,7 @@ from typing import Any
 
 from elbencho_amd import HTTP_PROTOCOL_VERSION
 from elbencho_amd.config import BenchConfig
+from elbencho_amd.dataprofile import DataProfile
 from elbencho_amd.stats import WorkerStats
 
 DEFAULT_PORT = 1611
@@ -398,6 +399,10 @@ class RemoteRunner:
                     # RemoteWorker::frameHostErrorMsg, RemoteWorker.cpp:650)
                     ws.error = f"[{hs.client.hostport}] {ws.error}"
                 host_workers.append(ws)
+            # --dataprofile: the service's merged profile (optional keys; a
+            # service that sends none contributes none)
+            if res.get("data_profile") and host_workers:
+                host_workers[0].data_profile = DataProfile.from_wire(res["data_profile"])
             all_workers.extend(host_workers)
             self.last_service_elapsed.append(
                 (hs.client.hostport,

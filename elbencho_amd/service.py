@@ -26,6 +26,7 @@ from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 from elbencho_amd import HTTP_PROTOCOL_VERSION, VERSION
 from elbencho_amd.config import BenchConfig
 from elbencho_amd.coordinator import LocalRunner
+from elbencho_amd.dataprofile import merge_profiles
 from elbencho_amd.stats import CpuUtil
 
 
@@ -42,6 +43,7 @@ class ServiceState:
         self.bench_id = ""
         self.phase_name = "IDLE"
         self.results: list[dict] | None = None
+        self.result_profile: dict | None = None  # --dataprofile, merged over the workers
         self.error: str = ""
         # recent error lines for master-side reporting (reference Logger
         # error history, Logger.h:33+)
@@ -94,6 +96,7 @@ class ServiceState:
             else:
                 self.runner = LocalRunner(cfg)
             self.results = None
+            self.result_profile = None
             self.error = ""
             self.phase_name = "IDLE"
             # BenchPathInfo (reference Common.h:214, returned from
@@ -114,6 +117,7 @@ class ServiceState:
             self.bench_id = bench_id
             self.phase_name = phase_name
             self.results = None
+            self.result_profile = None
             self.cpu = CpuUtil()
             self.runner.start(phase_name)
 
@@ -137,13 +141,21 @@ class ServiceState:
             if self.results is None:
                 self.runner.wait(-1)
                 workers = self.runner.finish()
-                self.results = [w.__dict__ for w in workers]
+                self.results = [{k: v for k, v in w.__dict__.items() if k != "data_profile"}
+                                for w in workers]
+                # --dataprofile: one profile per service, merged over its workers
+                merged = (None if any(w.error for w in workers)
+                          else merge_profiles(w.data_profile for w in workers))
+                self.result_profile = merged.to_wire() if merged else None
                 for w in workers:
                     if w.error:
                         self.err_history.append(f"{self.phase_name}: {w.error}")
                 self.phase_name = "IDLE"
-            return {"bench_id": self.bench_id, "workers": self.results,
-                    "error_history": list(self.err_history)}
+            res = {"bench_id": self.bench_id, "workers": self.results,
+                   "error_history": list(self.err_history)}
+            if self.result_profile is not None:
+                res["data_profile"] = self.result_profile
+            return res
 
     def interrupt(self) -> None:
         with self.lock:

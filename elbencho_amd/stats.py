@@ -22,6 +22,7 @@ from typing import Any
 
 from elbencho_amd import VERSION
 from elbencho_amd.config import BenchConfig, PATH_DIR
+from elbencho_amd.dataprofile import DataProfile, merge_profiles
 from elbencho_amd.histogram import Histogram
 from elbencho_amd.units import elapsed_ms_to_human
 
@@ -85,6 +86,7 @@ class WorkerStats:
     entry_lat_rm: list[int] = field(default_factory=list)
     error: str = ""
     num_workers: int = 1  # >1 when this row aggregates a remote service
+    data_profile: DataProfile | None = None  # --dataprofile, READ phases
 
     @classmethod
     def from_engine(cls, d: dict[str, Any]) -> "WorkerStats":
@@ -109,6 +111,8 @@ class WorkerStats:
             io_lat_rm=list(d.get("io_lat_rm", [])),
             entry_lat_rm=list(d.get("entry_lat_rm", [])),
             error=d["error"],
+            data_profile=(DataProfile.from_engine(d["data_profile"])
+                          if d.get("data_profile") else None),
         )
 
 
@@ -142,6 +146,7 @@ class PhaseResults:
     cpu_last: int = 0
     worker_elapsed_usec: list[int] = field(default_factory=list)
     errors: list[str] = field(default_factory=list)
+    data_profile: DataProfile | None = None  # --dataprofile: merged over the workers
 
     # --- derived ---
     def per_sec_last(self, value: int) -> int:
@@ -188,6 +193,9 @@ def aggregate_phase(phase_name: str, phase_id: str, start_time: float,
         r.worker_elapsed_usec.append(w.elapsed_usec)
         if w.error:
             r.errors.append(f"Rank {w.rank}: {w.error}")
+    # a phase in which a worker failed covered an unknown part of the data set
+    if not r.errors:
+        r.data_profile = merge_profiles(w.data_profile for w in workers)
     return r
 
 
@@ -282,6 +290,14 @@ def print_phase_results(cfg: BenchConfig, r: PhaseResults, out=None) -> None:
     if cfg.all_elapsed and r.worker_elapsed_usec:
         vals = " ".join(elapsed_ms_to_human(us // 1000) for us in r.worker_elapsed_usec)
         print(_fmt_row("", "Threads elapsed", "", vals), file=out)
+
+    if cfg.data_profile and r.phase_name == "READ":
+        if r.data_profile is None:
+            print(_fmt_row("", "data profile", "", "n/a"), file=out)
+        else:
+            print(_fmt_row("", "data profile", "", ""), file=out)
+            for label, value in r.data_profile.console_lines(cfg.dedupe_chunk):
+                print(_fmt_row("", "  " + label, "", value), file=out)
 
     for e in r.errors:
         print(f"ERROR: {e}", file=out)
@@ -510,6 +526,8 @@ def phase_results_json(cfg: BenchConfig, r: PhaseResults) -> dict[str, Any]:
         doc["label"] = cfg.label
     if r.errors:
         doc["errors"] = r.errors
+    if cfg.data_profile and r.data_profile is not None:
+        doc["dataProfile"] = r.data_profile.to_json(cfg.dedupe_chunk)
     return doc
 
 
